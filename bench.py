@@ -38,6 +38,11 @@ N > 1 (python -m torch.distributed.run ... bench.py --gpus N, C4 / C5):
     i.e. weak scaling in queries per GPU.
 
 Prints ONE JSON line on rank 0 (DESIGN.md §Measurement explains every field).
+A plain run builds the tree, warms up, times --steps steps and prints the
+headline fields (value, ms_per_step, config); --full adds the CPU baseline
+and parity legs, the latency passes, the roofline's profile pass and the
+index / directory figures, each an untimed pass of its own.  --dump-outputs
+DIR writes the last timed step's results as .npy files.
 """
 import argparse
 import json
@@ -87,7 +92,22 @@ def parse():
     p.add_argument("--scan-ratio", type=int, default=5, help="c5 range-scan percentage")
     p.add_argument("--scan-keys", type=int, default=100,
                    help="c5: expected stored keys per range scan")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also everything else the benchmark measures "
+                        "and checks: the CPU baseline and the parity batches, the per-batch "
+                        "and per-op latency passes, the roofline's profile pass and the "
+                        "index, directory and --insert-every figures.  Without it the run "
+                        "sets up, warms up, times the steps and prints the headline line "
+                        "(--cpu-seconds, --profile-steps, --latency-steps and --index-stats "
+                        "act only with --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned to "
+                        "its caller as DIR/<name>.npy (float64; c2 / c3: values and found of "
+                        "the step's gets, c5: counts and values of its scans; N > 1: "
+                        "<name>_rank<r>.npy; DUMP_MAX_VALUES elements in all, shared evenly "
+                        "among the arrays, each cut to its leading elements)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full without the CPU baseline and parity legs")
     p.add_argument("--cpu-seconds", type=float, default=10.0,
                    help="CPU baseline sample length (C1: >= 5 two-second windows)")
     p.add_argument("--sort", choices=("auto", "on", "off"), default="auto",
@@ -175,6 +195,12 @@ def parse():
         # the tree inside its arena)
         a.steps = (20 if a.workload == "c5" else
                    1000 if a.workload == "c2" and not a.insert_every else 200)
+    if a.profile_steps is None:
+        a.profile_steps = 60 if a.workload == "c5" else 10
+    if not a.full:
+        # the headline alone: none of the passes beside the timed steps
+        a.no_cpu_baseline, a.index_stats = True, False
+        a.profile_steps = a.latency_steps = 0
     return a
 
 
@@ -291,8 +317,6 @@ def build_shard(tree, n_keys, world, rank, dev):
 
 def main():
     args = parse()
-    if args.profile_steps is None:
-        args.profile_steps = 60 if args.workload == "c5" else 10
     if args.dir_extra_bits is not None:
         os.environ["SHM_DIR_EXTRA_BITS"] = str(args.dir_extra_bits)
     import torch
@@ -715,7 +739,8 @@ def main():
     torch.cuda.synchronize()
     if args.workload == "c2":
         last = (args.steps - 1) if world == 1 else seq[0] - 1  # last routed batch ended
-        hit_rate = float(outs[last % len(outs)][1].float().mean().item())
+        last_out = dict(zip(("values", "found"), outs[last % len(outs)]))
+        hit_rate = float(last_out["found"].float().mean().item())
     elif args.workload == "c5":
         for tot, cap in scan_out.pop("all", []):
             total, err = (int(x) for x in tot.cpu().tolist())
@@ -729,12 +754,73 @@ def main():
             tot_, flags = (int(x) for x in st.cpu().tolist())
             # every routed async batch complete: no run past its peer cap
             assert flags == 0, (tot_, flags)
-        c, _ = scan_out["r"].result()
+        c, v = scan_out["r"].result()
+        last_out = {"scan_counts": c, "scan_values": v}
         hit_rate = float(c.float().mean().item())  # mean values per scan
     else:
         last_b = (c3n[0] - 1) if c3_pipe else (args.steps - 1)  # the last step's batch
         n_get = mixed[last_b % N_BATCHES][0].numel()
+        last_out = {"values": vals[:n_get], "found": found[:n_get]}
         hit_rate = float(found[:n_get].float().mean().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, "" if world == 1 else "_rank%d" % rank, world)
+    # c3 / c5: the insert ordering ran one chunk ahead on its own stream
+    pipelined = (args.workload in ("c3", "c5") and args.pipeline and world == 1 and
+                 (args.workload == "c3" or bool(args.async_scans and
+                                                args.scan_out == "slots" and
+                                                args.streams == 2)))
+    out = None
+    if rank == 0:
+        # the headline line: the timed steps and the configuration they ran
+        metric, workload, data = describe(args, world, sim, s_rank, s_world)
+        out = {
+            "metric": metric,
+            "value": round(mops, 2),
+            "unit": "Mops/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "host_issue_ms_per_step": round(host_issue / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u64",
+            "data": data,
+            "full": bool(args.full),
+            "config": {
+                "workload": workload,
+                "keys_per_gpu": n_keys,
+                "batch_per_gpu": batch,
+                "tree_height": st["height"],
+                "pages": st["pages_used"],
+                "get_order": args.sort,
+                "streams": (len(outs) if args.workload == "c2" else
+                            args.streams if args.workload == "c5" and world == 1 else 1),
+                "rccl_groups": (len(outs) if args.workload == "c2" and world > 1 else None),
+                "router": router_kind,
+                "start": args.start,
+                "build_inserts_per_s": round(inserted / build_s, 1),
+                "hit_rate": round(hit_rate, 4),
+                "splits_in_timed_steps": st_end["splits"] - splits0,
+                "pages_after": st_end["pages_used"],
+            },
+            "cluster_sum_mops": round(cluster_sum, 2),
+        }
+        if args.workload == "c5":
+            out["config"]["hit_rate"] = None
+            out["config"]["values_per_scan"] = round(hit_rate, 2)
+            out["config"]["insert_pipeline"] = bool(pipelined)
+            out["config"]["scan_out"] = (("slots of %d values" % args.slot_cap)
+                                         if world == 1 and args.async_scans and
+                                         args.scan_out == "slots" else "compact")
+        if args.workload == "c3":
+            out["config"]["insert_pipeline"] = bool(pipelined)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        finish(dist, tree)
+        return
 
     # ---- per-batch latency (untimed pass): HIP events around each step on
     # its stream, in the order the reference reports them
@@ -835,69 +921,7 @@ def main():
                                    args.keys_log2, "k_get<" if page_walk else "k_get_sum")
 
     if rank == 0:
-        if args.workload == "c2":
-            metric = "batched get Mops/s (64M uint64 keys)"
-            workload = ("C2: batched get, 2^%d uint64 keys/GPU, uniform 100%% read, "
-                        "2^%d-query batches%s" % (args.keys_log2, args.batch_log2,
-                                                    "" if world == 1 else
-                                                    ", range shards + RCCL all-to-all"))
-            if sim:
-                workload += ", shard %d of %d (no exchange)" % (s_rank, s_world)
-            data = "synthetic: key(i)=CityHash64(i)+1, value=2i; uniform queries"
-            if ins is not None:
-                metric = "batched get + insert Mops/s (64M uint64 keys, a chunk of new keys " \
-                         "every %d get batches)" % args.insert_every
-                workload += (", + one 2^%d-key insert chunk of new keys (ids past the preload, "
-                             "value 2 id) after every %d get batches" % (args.batch_log2,
-                                                                        args.insert_every))
-        else:
-            metric = "mixed get/insert Mops/s (64M uint64 keys, zipf %.2f, %d%% get)" % (
-                args.theta, args.read_ratio)
-            workload = ("C3: 2^%d uint64 keys, 2^%d-op batches, key=to_key(1+zipf(%.2f)), "
-                        "%d%% get / %d%% insert (value = op index + 1)" % (
-                            args.keys_log2, args.batch_log2, args.theta, args.read_ratio,
-                            100 - args.read_ratio))
-            data = "synthetic: key(i)=CityHash64(i)+1 preload, zipf op stream"
-        if args.workload == "c5":
-            metric = ("write-heavy insert + range-scan Mops/s (zipf %.2f, %d%% insert, "
-                      "%d%% scan)" % (args.theta, 100 - args.scan_ratio, args.scan_ratio))
-            workload = ("C5: 2^%d uint64 keys/GPU, 2^%d-op batches/GPU, key=to_key(1+zipf(%.2f) "
-                        "over 2x the global key set), %d%% inserts (value = op index + 1), %d%% "
-                        "range scans of ~%d keys%s" % (
-                            args.keys_log2, args.batch_log2, args.theta, 100 - args.scan_ratio,
-                            args.scan_ratio, args.scan_keys,
-                            "" if world == 1 else ", range shards + RCCL all-to-all"))
-        out = {
-            "metric": metric,
-            "value": round(mops, 2),
-            "unit": "Mops/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "host_issue_ms_per_step": round(host_issue / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": data,
-            "config": {
-                "workload": workload,
-                "keys_per_gpu": n_keys,
-                "batch_per_gpu": batch,
-                "tree_height": st["height"],
-                "pages": st["pages_used"],
-                "get_order": args.sort,
-                "streams": (len(outs) if args.workload == "c2" else
-                            args.streams if args.workload == "c5" and world == 1 else 1),
-                "rccl_groups": (len(outs) if args.workload == "c2" and world > 1 else None),
-                "router": router_kind,
-                "start": args.start,
-                "build_inserts_per_s": round(inserted / build_s, 1),
-                "hit_rate": round(hit_rate, 4),
-                "splits_in_timed_steps": st_end["splits"] - splits0,
-                "pages_after": st_end["pages_used"],
-            },
+        out.update({
             "roofline": {
                 "bound": "hbm",
                 "achieved": round(achieved, 1),
@@ -939,8 +963,7 @@ def main():
             "batch_latency_us": dict(zip(("p50", "p90", "p95", "p99", "p99.9", "max"),
                                          [round(x, 1) for x in lat])),
             "op_latency_us": op_lat,
-            "cluster_sum_mops": round(cluster_sum, 2),
-        }
+        })
         if idx is not None:
             out["index_stats"] = idx
         if dirst is not None:
@@ -990,10 +1013,6 @@ def main():
             per = {"ops": prof["insert_ops"] / ic, "uniq": prof["insert_unique"] / ic,
                    "dels": prof["insert_dels"] / ic, "staged": prof["insert_staged"] / ic,
                    "new_pages": prof_new_pages / ic}
-            pipelined = (args.pipeline and world == 1 and
-                         (args.workload == "c3" or bool(args.async_scans and
-                                                        args.scan_out == "slots" and
-                                                        args.streams == 2)))
             # the profiled window: the tree phase alone when pipelined (the
             # ordering ran a step earlier on its own stream), else the chunk
             alg_win = insert_alg_bytes(per["ops"], per["uniq"], per["dels"], per["staged"],
@@ -1026,12 +1045,6 @@ def main():
                                        if ins["traffic_GBps"] else None)
             cap_fracs(ins, ("alg_frac", "traffic_frac"))
         if args.workload == "c5":
-            out["config"]["hit_rate"] = None
-            out["config"]["values_per_scan"] = round(hit_rate, 2)
-            out["config"]["insert_pipeline"] = bool(pipelined)
-            out["config"]["scan_out"] = (("slots of %d values" % args.slot_cap)
-                                         if world == 1 and args.async_scans and
-                                         args.scan_out == "slots" else "compact")
             rf = out["roofline"]
             for k in ("walk_ms_per_launch", "walk_ms_basis", "walk_clock_ms_per_launch",
                       "order_ms_per_launch", "queries_per_launch",
@@ -1060,7 +1073,6 @@ def main():
             step_s = elapsed / args.steps
             b0 = mixed[0]
             alg = b0[0].numel() * bpg + alg_chunk
-            out["config"]["insert_pipeline"] = bool(args.pipeline and world == 1)
             rf = out["roofline"]
             rf["insert"] = ins
             rf["walk_frac"] = rf["frac"]  # the get walk alone (k_get_sum), as C2
@@ -1080,10 +1092,72 @@ def main():
                                     "reference_bytes_frac", "request_frac", "alg_frac",
                                     "traffic_frac"))
         print(json.dumps(out), flush=True)
+    finish(dist, tree)
+
+
+def finish(dist, tree):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     tree.close()
+
+
+def describe(args, world, sim, s_rank, s_world):
+    """(metric, workload, data) of the result line."""
+    if args.workload == "c5":
+        metric = ("write-heavy insert + range-scan Mops/s (zipf %.2f, %d%% insert, "
+                  "%d%% scan)" % (args.theta, 100 - args.scan_ratio, args.scan_ratio))
+        workload = ("C5: 2^%d uint64 keys/GPU, 2^%d-op batches/GPU, key=to_key(1+zipf(%.2f) "
+                    "over 2x the global key set), %d%% inserts (value = op index + 1), %d%% "
+                    "range scans of ~%d keys%s" % (
+                        args.keys_log2, args.batch_log2, args.theta, 100 - args.scan_ratio,
+                        args.scan_ratio, args.scan_keys,
+                        "" if world == 1 else ", range shards + RCCL all-to-all"))
+        return metric, workload, "synthetic: key(i)=CityHash64(i)+1 preload, zipf op stream"
+    if args.workload == "c3":
+        metric = "mixed get/insert Mops/s (64M uint64 keys, zipf %.2f, %d%% get)" % (
+            args.theta, args.read_ratio)
+        workload = ("C3: 2^%d uint64 keys, 2^%d-op batches, key=to_key(1+zipf(%.2f)), "
+                    "%d%% get / %d%% insert (value = op index + 1)" % (
+                        args.keys_log2, args.batch_log2, args.theta, args.read_ratio,
+                        100 - args.read_ratio))
+        return metric, workload, "synthetic: key(i)=CityHash64(i)+1 preload, zipf op stream"
+    metric = "batched get Mops/s (64M uint64 keys)"
+    workload = ("C2: batched get, 2^%d uint64 keys/GPU, uniform 100%% read, "
+                "2^%d-query batches%s" % (args.keys_log2, args.batch_log2,
+                                            "" if world == 1 else
+                                            ", range shards + RCCL all-to-all"))
+    if sim:
+        workload += ", shard %d of %d (no exchange)" % (s_rank, s_world)
+    if args.insert_every:
+        metric = "batched get + insert Mops/s (64M uint64 keys, a chunk of new keys " \
+                 "every %d get batches)" % args.insert_every
+        workload += (", + one 2^%d-key insert chunk of new keys (ids past the preload, "
+                     "value 2 id) after every %d get batches" % (args.batch_log2,
+                                                                args.insert_every))
+    return metric, workload, "synthetic: key(i)=CityHash64(i)+1, value=2i; uniform queries"
+
+
+DUMP_MAX_VALUES = 6 << 20   # elements in all dumped arrays of all ranks (float64: 48 MiB)
+
+
+def dump_outputs(path, arrays, suffix, world=1):
+    """--dump-outputs: the last timed step's results as float64 .npy files.
+    The values are 2 id or an op index + 1, far below 2^53, so float64 holds
+    them exactly (checked).  DUMP_MAX_VALUES elements are shared evenly among
+    the arrays of the `world` ranks; an array past its share (a C5 step's
+    scan values; C2 from N = 4 on) is cut to its leading elements, in query /
+    scan order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_VALUES // (world * len(arrays))
+    for name, t in arrays.items():
+        a = t.reshape(-1)[:share].cpu().numpy()
+        if a.dtype == np.int64:
+            a = a.view(np.uint64)
+            if a.size and int(a.max()) >= 1 << 53:
+                raise ValueError(f"--dump-outputs: {name} holds a value past 2^53")
+        np.save(os.path.join(path, name + suffix + ".npy"), a.astype(np.float64))
 
 
 def rewarm(tree, dev, seconds=0.5):

@@ -10,6 +10,6 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export SHM_BENCH_REGION=timed
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run \
-  -- python3 $R/bench.py --workload c5 --no-cpu-baseline --latency-steps 0 --profile-steps 0 "$@" \
+  -- python3 $R/bench.py --workload c5 "$@" \
   > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python3 $R/tools/window_stats.py $OUT/trace/run_kernel_trace.csv

@@ -22,16 +22,16 @@ for w in $WHAT; do
          timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 \
            || { cat $OUT/smoke.log; exit 1; }
          cat $OUT/smoke.log ;;
-    bench) timeout -k 10 500 python -u bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err \
+    bench) timeout -k 10 500 python -u bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err \
            || { tail -30 $OUT/bench_c2.err; exit 1; }
          cat $OUT/bench_c2.json ;;
-    ie) timeout -k 10 500 python -u bench.py --insert-every 8 > $OUT/bench_ie.json 2> $OUT/bench_ie.err \
+    ie) timeout -k 10 500 python -u bench.py --full --insert-every 8 > $OUT/bench_ie.json 2> $OUT/bench_ie.err \
            || { tail -30 $OUT/bench_ie.err; exit 1; }
          cat $OUT/bench_ie.json ;;
-    pchk) timeout -k 10 500 python -u bench.py --page-check 1 --no-cpu-baseline > $OUT/bench_pchk.json 2> $OUT/bench_pchk.err \
+    pchk) timeout -k 10 500 python -u bench.py --full --page-check 1 --no-cpu-baseline > $OUT/bench_pchk.json 2> $OUT/bench_pchk.err \
            || { tail -30 $OUT/bench_pchk.err; exit 1; }
          cat $OUT/bench_pchk.json ;;
-    c3|c5) timeout -k 10 500 python -u bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err \
+    c3|c5) timeout -k 10 500 python -u bench.py --full --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err \
            || { tail -30 $OUT/bench_$w.err; exit 1; }
          cat $OUT/bench_$w.json ;;
   esac

@@ -17,7 +17,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 CAL=$R/tools/_build/cal_fetch
 STEPS=50
-B="$R/bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --profile-steps 0 --latency-steps 0"
+B="$R/bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --profile-steps 0 --latency-steps 0"
 timeout -k 10 120 $CAL > $OUT/cal.jsonl 2> $OUT/cal.err || exit $?
 cat $OUT/cal.jsonl
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/cal_fetch -o run \

@@ -11,7 +11,7 @@ cd $R
 for w in c2 c5; do
   SHM_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) \
-    bench.py --gpus $N --steps 5 --warmup 2 --keys-log2 $KL --workload $w \
+    bench.py --full --gpus $N --steps 5 --warmup 2 --keys-log2 $KL --workload $w \
     > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail -40 $OUT/bench_$w.err; exit 1; }
   cat $OUT/bench_$w.json
 done

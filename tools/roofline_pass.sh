@@ -22,7 +22,7 @@ OUT=$R/gpurun_out/roof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for W in $WLS; do
-  B="$R/bench.py --workload $W --no-cpu-baseline --latency-steps 0"
+  B="$R/bench.py --full --workload $W --no-cpu-baseline --latency-steps 0"
   S="--steps 20 --warmup 3"
   [ $W = c5 ] && S="--steps 10 --warmup 3"
   timeout -k 10 400 python3 $B > $OUT/bench_$W.json 2> $OUT/bench_$W.err || { tail -20 $OUT/bench_$W.err; exit 1; }

@@ -1,6 +1,8 @@
 """Per-step kernel timeline of the timed C2 steps, from a rocprofv3 kernel
-trace of `bench.py --profile-steps 0 --latency-steps 0 --no-cpu-baseline`
-(the default two-stream run, i.e. the timed condition):
+trace of a plain `bench.py` run, or of `bench.py --full --profile-steps 0
+--latency-steps 0 --no-cpu-baseline`, whose line also has the roofline
+fields tools/fold_c2.py reads (the default two-stream run, i.e. the timed
+condition):
 
     python tools/step_timeline.py TRACE.csv STEPS [KERNEL] [bench.json] [pmc_fetch.csv]
 
