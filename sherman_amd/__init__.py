@@ -576,10 +576,11 @@ class Tree:
     def dir_verify(self):
         """Diagnostics (shm__dir_verify): every directory entry the walks
         trust checked against the tree as it is now."""
-        out = (u64 * 8)()
+        out = (u64 * 10)()
         _check(_hooks().shm__dir_verify(self.h, out), "dir_verify")
         return {"checked": out[0], "bad_lists": out[1], "bad_pairs": out[2], "bad_fps": out[3],
-                "first_bad": [x - 1 for x in out[4:8] if x]}
+                "first_bad": [x - 1 for x in out[4:8] if x],
+                "vals_checked": out[8], "bad_vals": out[9]}
 
     def profile_read(self, reset=True):
         p = ShmProfile()

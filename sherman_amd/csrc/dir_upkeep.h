@@ -20,7 +20,14 @@
 //     (kDirPairsBad, or kDirFp cleared) (dir_note_split_page);
 //   * an entry neither rule keeps exact (a shared prefix, a new key whose
 //     leaf its list does not name) is marked kDirFix and listed, and after
-//     the chunk k_dir_repair (leafdir.hip) rebuilds it from the tree.
+//     the chunk k_dir_repair (leafdir.hip) rebuilds it from the tree;
+//   * a value-form entry (layout.h kDirVals) carries its keys' values, which
+//     an exact directory's get trusts without reading the leaf: a new key at
+//     pair position 0 or 1 adds its inline copy, a split page's rewrite and
+//     the repair write the form, and a key the chunk updated in place or
+//     deleted lists its entry for the repair (dir_note_changed).  Here the
+//     upkeep IS about results: a chunk that skips it ends the directory's
+//     exactness (tree.cpp), and the gets then ignore the form.
 // Every entry a get trusts still only names slots to read: a get that does
 // not find its key there walks the summary path (get.hip), so the upkeep is
 // about cost, never about results.  Prefixes of a split page without keys
@@ -87,8 +94,41 @@ __device__ __forceinline__ void dir_note_stale_lanes(const UpperArgs& u, bool wa
   }
 }
 
-// key k was stored in the empty slot s of leaf page index pg (one lane)
-__device__ __forceinline__ void dir_note_new(const UpperArgs& u, uint64_t k, uint32_t pg, int s) {
+// the inline (key, value) of pair q < kDirValMax of a value-form entry
+// (layout.h kDirVals)
+__device__ __forceinline__ void dir_val_put(uint32_t* w, uint32_t q, uint64_t k, uint64_t v) {
+  uint32_t* kw = q == 0 ? w + 2 : w + 12;
+  uint32_t* vw = q == 0 ? w + 5 : w + 14;
+  kw[0] = (uint32_t)k;
+  kw[1] = (uint32_t)(k >> 32);
+  vw[0] = (uint32_t)v;
+  vw[1] = (uint32_t)(v >> 32);
+}
+__device__ __forceinline__ uint64_t dir_val_key(const uint32_t* w, uint32_t q) {
+  const uint32_t* kw = q == 0 ? w + 2 : w + 12;
+  return (uint64_t)kw[0] | ((uint64_t)kw[1] << 32);
+}
+
+// key k was updated in place or deleted by this chunk (one lane): a
+// value-form entry that carries it would serve the old value, so it is
+// listed for the repair after the chunk, which rebuilds it from the tree
+// (marking is safe against a split page's rewrite of the same entry in this
+// launch: a fresh entry marked late is only rebuilt once more)
+__device__ __forceinline__ void dir_note_changed(const UpperArgs& u, uint64_t k) {
+  uint32_t* w = u.dir_w && u.dir_form == kDirFormPairs
+                    ? dir_entry_w(u.dir_w, u.dir_lo, u.dir_shift, u.dir_n, k)
+                    : nullptr;
+  if (!w) return;
+  const uint32_t cw = w[7];
+  if (!dir_vals_usable(cw)) return;
+  const uint32_t np = (cw >> 16) & 0xFFu;
+  if ((np > 0 && dir_val_key(w, 0) == k) || (np > 1 && dir_val_key(w, 1) == k))
+    dir_note_stale(u, w, dir_prefix(u, w));
+}
+
+// key k (value v) was stored in the empty slot s of leaf page index pg (one lane)
+__device__ __forceinline__ void dir_note_new(const UpperArgs& u, uint64_t k, uint64_t v,
+                                             uint32_t pg, int s) {
   uint32_t* w = u.dir_w ? dir_entry_w(u.dir_w, u.dir_lo, u.dir_shift, u.dir_n, k) : nullptr;
   if (!w) return;
   // a plain load: this chunk's other writers only add pairs or flags
@@ -104,11 +144,24 @@ __device__ __forceinline__ void dir_note_new(const UpperArgs& u, uint64_t k, uin
       return;
     }
     const uint32_t pos = (atomicAdd(w + 7, 1u << 16) >> 16) & 0xFFu;
+    // An entry built in value form (kDirVals; its leaf count <= 2 leaves
+    // the inline words free) keeps the flag for good: the first kDirValMax
+    // pairs carry their entries, and a pair count past that ends the form by
+    // itself (dir_vals_usable), so no lane ever clears the flag under
+    // another lane's feet.  The second inline entry lies where pairs 8..15
+    // would: a lane that would write one of those -- perhaps in this very
+    // launch, beside the lane still writing that inline entry -- hands the
+    // entry to the repair instead, which rebuilds it in plain pair form.
+    if ((cw & kDirVals) && pos >= 8) {
+      dir_note_stale(u, w, dir_prefix(u, w));
+      return;
+    }
     if (pos < kDirPairMax)
       reinterpret_cast<uint16_t*>(w + 8)[pos] =
           (uint16_t)(key_fp(k) | (((uint32_t)s | ((uint32_t)j << 6)) << 8));
     else
       atomicOr(w + 7, kDirPairsBad);  // more keys than pairs: unusable (as a build leaves it)
+    if ((cw & kDirVals) && pos < kDirValMax) dir_val_put(w, pos, k, v);
   } else if (u.dir_form == kDirFormFp && (cw & kDirFp)) {
     if (w[0] == pg)
       reinterpret_cast<uint8_t*>(w)[dir_fp_byte(s)] = (uint8_t)key_fp(k);
@@ -124,7 +177,7 @@ __device__ __forceinline__ void dir_note_new(const UpperArgs& u, uint64_t k, uin
 // the shared ones.
 __device__ __forceinline__ void dir_note_split_page(const UpperArgs& u, uint32_t pg,
                                                     uint64_t lowest, uint64_t highest,
-                                                    uint64_t key, uint32_t c) {
+                                                    uint64_t key, uint64_t val, uint32_t c) {
   if (!u.dir_w || u.dir_form == kDirFormNone) return;
   const int lane = lane_id();
   const uint64_t lo = u.dir_lo;
@@ -165,6 +218,12 @@ __device__ __forceinline__ void dir_note_split_page(const UpperArgs& u, uint32_t
     }
     const uint32_t cnt = (uint32_t)popc64(m);
     uint32_t v = 0;
+    // the value form (layout.h kDirVals): at most kDirValMax keys, every one
+    // valid (a key this chunk deleted keeps its slot with value 0)
+    const bool vf = u.dir_vals && cnt <= kDirValMax && (m & ballot(val == kValueNull)) == 0;
+    const uint64_t vk0 = shfl64(key, first), vv0 = shfl64(val, first);
+    const uint64_t vk1 = shfl64(key, first + 1 < 64 ? first + 1 : 63);
+    const uint64_t vv1 = shfl64(val, first + 1 < 64 ? first + 1 : 63);
     if (u.dir_form == kDirFormPairs) {
       // words 0..7: {pg, 0 x 6, 1 leaf | kDirPairs | pairs << 16}; words
       // 8..15: pairs 2x and 2x + 1 = the prefix's keys in slot order
@@ -174,11 +233,23 @@ __device__ __forceinline__ void dir_note_split_page(const UpperArgs& u, uint32_t
       const uint32_t f0 = shfl32(fp, s0 < 63 ? s0 : 62);
       const uint32_t f1 = shfl32(fp, s0 + 1 < 64 ? s0 + 1 : 63);
       if (lane == 0) v = pg;
-      if (lane == 7) v = 1u | kDirPairs | ((cnt < 255u ? cnt : 255u) << 16);
+      if (lane == 7) v = 1u | kDirPairs | ((cnt < 255u ? cnt : 255u) << 16) | (vf ? kDirVals : 0u);
       if (lane >= 8 && lane < 16) {
         if (q0 < cnt && q0 < kDirPairMax) v |= (f0 & 0xFFu) | ((uint32_t)s0 << 8);
         if (q0 + 1 < cnt && q0 + 1 < kDirPairMax)
           v |= ((f1 & 0xFFu) | ((uint32_t)(s0 + 1) << 8)) << 16;
+      }
+      if (vf) {  // (cnt >= 1: the prefix holds key `first`)
+        if (lane == 2) v = (uint32_t)vk0;
+        if (lane == 3) v = (uint32_t)(vk0 >> 32);
+        if (lane == 5) v = (uint32_t)vv0;
+        if (lane == 6) v = (uint32_t)(vv0 >> 32);
+        if (cnt > 1) {
+          if (lane == 12) v = (uint32_t)vk1;
+          if (lane == 13) v = (uint32_t)(vk1 >> 32);
+          if (lane == 14) v = (uint32_t)vv1;
+          if (lane == 15) v = (uint32_t)(vv1 >> 32);
+        }
       }
     } else {
       v = fpw;
@@ -226,7 +297,7 @@ __device__ __forceinline__ void dir_note_split_page(const UpperArgs& u, uint32_t
   if (u.dir_form == kDirFormPairs) {
 #pragma unroll
     for (int x = 1; x < 16; ++x) body[x] = 0u;
-    body[7] = 1u | kDirPairs;
+    body[7] = 1u | kDirPairs | (u.dir_vals ? kDirVals : 0u);  // (no key: no inline copy)
   } else {
     body[7] = 1u | kDirFp;
   }

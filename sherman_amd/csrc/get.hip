@@ -393,6 +393,26 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k
       // point, or more matching pairs than the lane queues, walks anyway)
       const bool exact_miss = a.dir_exact && ((fpform && pok) || (pu && alt == 0 &&
                                                                   __builtin_popcount(pc) <= 8));
+      // the value form (layout.h kDirVals): an exact directory's entry of a
+      // prefix of at most two keys carries them whole, so the get ends with
+      // its first request -- the key's value, or absent by the rule above.
+      // Not with PCHK (no page read, no versions to check).
+      if (!PCHK && a.dir_exact && pu && dir_vals_usable(e[1].w)) {
+        const uint32_t np = (e[1].w >> 16) & 0xFFu;
+        const uint64_t k0 = (uint64_t)e[0].z | ((uint64_t)e[0].w << 32);
+        const uint64_t v0 = (uint64_t)e[1].y | ((uint64_t)e[1].z << 32);
+        const uint64_t k1 = (uint64_t)e[3].x | ((uint64_t)e[3].y << 32);
+        const uint64_t v1 = (uint64_t)e[3].z | ((uint64_t)e[3].w << 32);
+        if (np > 0 && k0 == k && v0 != kValueNull) {
+          val = v0;
+          hit = done = true;
+        } else if (np > 1 && k1 == k && v1 != kValueNull) {
+          val = v1;
+          hit = done = true;
+        } else if (exact_miss) {
+          done = true;
+        }
+      }
       // pend: the lane's candidate slots of its leaf still to read, lowest
       // first; a pair lane's candidates instead as up to 8 packed bytes
       // (leaf << 6 | slot) in plist, with the leaves' pages in lpg (the
@@ -402,7 +422,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k
       uint64_t plist = 0;
       uint32_t pn = 0;
       const uint32_t lpg[4] = {e[0].x, e[0].y, e[0].z, e[0].w};
-      if (pu) {
+      if (pu && !done) {
 #pragma unroll
         for (int j = 0; j < (int)kDirPairMax; ++j) {
           if (((pc >> j) & 1u) && pn < 8) {
@@ -438,7 +458,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k
       };
       RawEntry r1;
       bool l1 = false;
-      const bool any1 = pend || pn;
+      const bool any1 = !done && (pend || pn);
       if (any1) {
         l1 = next();
         if (l1) entry_load(cp, cs, r1);

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(kUpT) __attribute__((amdgpu_waves_per_eu(3))) void 
       sb->batches = a.batch;
       // no block of this launch reads the op buffers or the ordering's
       // counts on this path
-      if (a.pub)
+      if (a.pub && !a.pub_later)
         __hip_atomic_store(a.pub + kPubApplied, a.batch, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -590,7 +590,8 @@ __global__ __launch_bounds__(kUpT) __attribute__((amdgpu_waves_per_eu(3))) void 
     if (__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~kErrKeyMax)
       atomicCAS(a.err + 1, 0u, (uint32_t)a.batch);
     // every block has finished (the `done` count): the op buffers are free
-    if (a.pub)
+    // (pub_later: the directory upkeep still reads them)
+    if (a.pub && !a.pub_later)
       __hip_atomic_store(a.pub + kPubApplied, a.batch, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_SYSTEM);
   }

@@ -132,13 +132,17 @@ void launch_leaf_dir(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, 
 // the pairs of a pair-form directory: one wave per page of [1, n_pages)
 void launch_dir_pairs(const uint8_t* arena, uint64_t n_pages, uint16_t node, uint64_t dir_lo,
                       uint32_t shift, uint64_t n_ent, uint64_t* dir, hipStream_t s);
+// the value form after the pairs (layout.h kDirVals): one thread per entry
+void launch_dir_vals(const uint8_t* arena, uint64_t n_pages, uint64_t n_ent, uint64_t* dir,
+                     hipStream_t s);
 // rebuild the entries an insert chunk listed (fix[0 .. fix_n[par]), at most
 // cap) from the tree, in form `form` (kDirForm*); zeroes fix_n[par ^ 1]; the
 // repairs past cap are added to *lost (host memory, nullable)
 void launch_dir_repair(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, uint64_t root,
                        uint64_t dir_lo, uint32_t shift, uint64_t n_ent, uint64_t* dir,
                        const uint32_t* hint, int form, const uint32_t* fix, uint32_t* fix_n,
-                       uint32_t par, uint32_t cap, uint64_t* lost, uint32_t* err, hipStream_t s);
+                       uint32_t par, uint32_t cap, uint64_t* lost, uint32_t* err, hipStream_t s,
+                       int vals = 0, uint64_t applied = 0);
 struct UpperArgs;
 // per-op word of the upsert (SegArgs.placed): the op's new key went into an
 // empty slot of its leaf, the slot in the low 6 bits
@@ -148,8 +152,9 @@ constexpr uint32_t kOpPlaced = 0x40000000u;
 // the split segments; n_max bounds both counts (the grid)
 void launch_dir_upkeep(const UpperArgs& u, const uint32_t* oslot, const uint64_t* pages,
                        const uint64_t* n_ops_dev, uint64_t n_max, hipStream_t s);
-// diagnostics: the trusted entries against the tree (k_dir_verify): out = 8
-// words, zeroed by the caller
+// diagnostics: the trusted entries against the tree (k_dir_verify): out =
+// kDirVerifyWords words, zeroed by the caller
+constexpr int kDirVerifyWords = 10;
 void launch_dir_verify(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, uint64_t root,
                        uint64_t dir_lo, uint32_t shift, uint64_t n_ent, const uint64_t* dir,
                        const uint32_t* hint, unsigned long long* out, hipStream_t s);
@@ -333,6 +338,8 @@ struct UpperArgs {
   // k_dir_upkeep in form dir_form (dir_upkeep.h: 1 fingerprint, 2 pair form)
   uint64_t* dir_w;
   uint32_t dir_form;
+  // pair form: the upkeep writes and keeps the value form (layout.h kDirVals)
+  uint32_t dir_vals;
   // the chunk's repair list (nullable): prefixes whose entries the upkeep
   // could not keep exact, for k_dir_repair after it; dir_fix_n[par]
   // counts them (past dir_fix_cap they are lost: the entry stays marked)
@@ -360,6 +367,11 @@ struct UpperArgs {
   // publish the chunk's tag in the host mirror even without new pages (the
   // host's directory is behind the tree and it watches for a quiet tree)
   uint32_t pub_always;
+  // k_dir_upkeep follows this chunk's k_upper and reads the op buffers and
+  // the ordering's counts after it: the word kPubApplied (the buffers are
+  // free) is then published by k_dir_repair, which runs after the upkeep,
+  // and not by the kernel that completes the chunk
+  uint32_t pub_later;
 };
 constexpr int kUpperStamps = 32;
 // diagnostic clock words: k_upper's, then k_bin_unique's 8 phases x kCoarse bins

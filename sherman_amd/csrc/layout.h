@@ -96,6 +96,25 @@ constexpr uint32_t kDirPairMax = 16;
 // count word flag: an insert chunk's writer listed the entry for repair
 // after the chunk (dir_upkeep.h, leafdir.hip k_dir_repair); the walks ignore it
 constexpr uint32_t kDirFix = 0x800u;
+// value form of a usable pair-form entry (count word flag, with kDirPairs):
+// the prefix holds at most kDirValMax valid keys in at most two leaves, and
+// the entry carries them whole -- pair q's (key, value) inline for q < the
+// pair count: key0 in words 2..3, value0 in words 5..6 (pg2 / pg3 / t2 / t3,
+// which a leaf count <= 2 leaves unread), key1 and value1 in bytes 48..63
+// (pairs 8..15, unused at <= 2 pairs).  The pairs stay at bytes 32..35.  An
+// exact directory's get of such a prefix is answered by the entry alone
+// (get.hip).  While the entry is usable and its pair count is <= kDirValMax
+// the copies equal the tree (dir_upkeep.h); a third key ends the form
+// through the count, the flag itself stays (it then only says that bytes
+// 48..63 are not pair slots: the entry holds 8 pairs until a repair or a
+// split rewrites it)
+constexpr uint32_t kDirVals = 0x1000u;
+constexpr uint32_t kDirValMax = 2;
+// a count word whose entry is in usable value form
+SHM_HD bool dir_vals_usable(uint32_t cw) {
+  return (cw & (kDirVals | kDirPairs | kDirPairsBad | kDirFix)) == (kDirVals | kDirPairs) &&
+         ((cw >> 16) & 0xFFu) <= kDirValMax && (cw & 0xFFu) <= 2u;
+}
 SHM_HD uint32_t key_fp(uint64_t k) {
   const uint32_t f = (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 56);
   return f ? f : 1u;

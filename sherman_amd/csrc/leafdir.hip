@@ -259,6 +259,56 @@ void launch_dir_pairs(const uint8_t* arena, uint64_t n_pages, uint16_t node, uin
                      shift, n_ent, dir);
 }
 
+// The value form (layout.h kDirVals) after k_dir_pairs, one thread per
+// prefix: a usable pair-form entry of at most kDirValMax pairs and two leaves
+// gets the (key, value) of each pair's slot inline and the flag.
+__device__ __forceinline__ void dir_put_val(uint32_t* w, uint32_t q, uint64_t k, uint64_t v) {
+  if (q == 0) {
+    w[2] = (uint32_t)k;
+    w[3] = (uint32_t)(k >> 32);
+    w[5] = (uint32_t)v;
+    w[6] = (uint32_t)(v >> 32);
+  } else {
+    w[12] = (uint32_t)k;
+    w[13] = (uint32_t)(k >> 32);
+    w[14] = (uint32_t)v;
+    w[15] = (uint32_t)(v >> 32);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dir_vals(const uint8_t* __restrict__ arena,
+                                                  uint64_t n_pages, uint64_t n_ent,
+                                                  uint64_t* __restrict__ dir) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_ent) return;
+  uint32_t* w = reinterpret_cast<uint32_t*>(dir + kDirWords * p);
+  const uint32_t cw = w[7];
+  if (!dir_vals_usable(cw | kDirVals)) return;
+  const uint32_t np = (cw >> 16) & 0xFFu;
+  const uint32_t prs = w[8];
+  uint64_t k[kDirValMax] = {0, 0}, v[kDirValMax] = {0, 0};
+  for (uint32_t q = 0; q < np; ++q) {
+    const uint32_t pr = (prs >> (16 * q)) & 0xFFFFu;
+    const uint32_t leaf = (pr >> 14) & 3u;
+    const uint32_t pg = leaf < (cw & 0xFFu) ? w[leaf] : 0u;
+    const uint32_t sl = (pr >> 8) & 63u;
+    // (a pair k_dir_pairs did not write: the entry stays in plain pair form)
+    if (pg == 0 || pg >= n_pages || sl >= (uint32_t)kLeafCardinality) return;
+    uint32_t f, r;
+    lane_entry(arena + ((uint64_t)pg << 10), (int)sl, k[q], v[q], f, r);
+    if (v[q] == kValueNull || ((f ^ r) & 0xF) != 0 || key_fp(k[q]) != (pr & 0xFFu)) return;
+  }
+  for (uint32_t q = 0; q < np; ++q) dir_put_val(w, q, k[q], v[q]);
+  w[7] = cw | kDirVals;
+}
+
+void launch_dir_vals(const uint8_t* arena, uint64_t n_pages, uint64_t n_ent, uint64_t* dir,
+                     hipStream_t s) {
+  if (n_pages <= 1 || !n_ent) return;
+  hipLaunchKernelGGL(k_dir_vals, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, s, arena,
+                     n_pages, n_ent, dir);
+}
+
 // The exact entry of prefix p as a build would write it (one wave): word
 // `lane` of the 64 B entry in *v for lanes < 16; false when the walk failed
 // (a bad pointer).  In the pair form *np_out = the pair count.
@@ -267,7 +317,7 @@ __device__ __forceinline__ bool dir_exact_entry(const uint8_t* __restrict__ aren
                                                 uint64_t dir_lo, uint32_t shift, uint64_t p,
                                                 const uint32_t* __restrict__ hint, int form,
                                                 uint32_t* v_out, uint32_t* np_out,
-                                                bool prefix_fps = false) {
+                                                bool prefix_fps = false, bool vals = false) {
   const int lane = lane_id();
   const uint64_t span = (1ull << shift) - 1;
   const uint32_t sh = shift > 32 ? shift - 32 : 0;
@@ -375,6 +425,7 @@ __device__ __forceinline__ bool dir_exact_entry(const uint8_t* __restrict__ aren
       uint32_t np = 0;
       uint32_t pos[4] = {~0u, ~0u, ~0u, ~0u};  // this lane's (slot's) pair position in leaf j
       uint32_t pr[4] = {0, 0, 0, 0};
+      uint64_t qk[kDirValMax] = {0, 0}, qv[kDirValMax] = {0, 0};  // the first pairs' entries
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if ((uint32_t)j >= n) break;
@@ -388,6 +439,14 @@ __device__ __forceinline__ bool dir_exact_entry(const uint8_t* __restrict__ aren
         if (in) {
           pos[j] = np + (uint32_t)popc64(b & lanemask_lt());
           pr[j] = key_fp(k) | (((uint32_t)lane | ((uint32_t)j << 6)) << 8);
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < kDirValMax; ++q) {
+          const uint64_t bq = ballot(pos[j] == q);
+          if (bq) {
+            qk[q] = shfl64(k, ctz64(bq));
+            qv[q] = shfl64(val, ctz64(bq));
+          }
         }
         np += (uint32_t)popc64(b);
       }
@@ -411,6 +470,17 @@ __device__ __forceinline__ bool dir_exact_entry(const uint8_t* __restrict__ aren
       if (lane >= 8 && lane < 16) v = (lo16 & 0xFFFFu) | ((hi16 & 0xFFFFu) << 16);
       cw |= kDirPairs | ((np < 255u ? np : 255u) << 16);
       *np_out = np;
+      if (vals && np <= kDirValMax && n <= 2) {  // the value form (layout.h kDirVals)
+        cw |= kDirVals;
+        if (lane == 2) v = (uint32_t)qk[0];
+        if (lane == 3) v = (uint32_t)(qk[0] >> 32);
+        if (lane == 5) v = (uint32_t)qv[0];
+        if (lane == 6) v = (uint32_t)(qv[0] >> 32);
+        if (lane == 12) v = (uint32_t)qk[1];
+        if (lane == 13) v = (uint32_t)(qk[1] >> 32);
+        if (lane == 14) v = (uint32_t)qv[1];
+        if (lane == 15) v = (uint32_t)(qv[1] >> 32);
+      }
     }
     if (lane == 7) v = cw;
   }
@@ -438,12 +508,19 @@ __global__ __launch_bounds__(256) void k_dir_repair(const uint8_t* __restrict__ 
                                                     const uint32_t* __restrict__ hint, int form,
                                                     const uint32_t* __restrict__ fix,
                                                     uint32_t* fix_n, uint32_t par, uint32_t cap,
-                                                    uint64_t* lost, uint32_t* err) {
+                                                    uint64_t* lost, uint32_t* err, int vals,
+                                                    uint64_t applied) {
   const int lane = lane_id();
   const uint32_t n_fix = fix_n[par];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     fix_n[par ^ 1u] = 0;  // the next chunk's list (its writers run after this launch)
     if (lost) {
+      // k_dir_upkeep, the last reader of the chunk's op buffers and counts,
+      // has finished: they are free (UpperArgs.pub_later; `lost` is the
+      // mirror's word kPubDirLost)
+      if (applied)
+        __hip_atomic_store(lost - kPubDirLost + kPubApplied, applied, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
       if (n_fix > cap) {
         const uint64_t l = __hip_atomic_load(lost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(lost, l + (n_fix - cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -465,7 +542,8 @@ __global__ __launch_bounds__(256) void k_dir_repair(const uint8_t* __restrict__ 
     if (p >= n_ent) continue;
     uint32_t* w = reinterpret_cast<uint32_t*>(dir + kDirWords * p);
     uint32_t v = 0, np = 0;
-    if (!dir_exact_entry(arena, arena_bytes, node, root, dir_lo, shift, p, hint, form, &v, &np)) {
+    if (!dir_exact_entry(arena, arena_bytes, node, root, dir_lo, shift, p, hint, form, &v, &np,
+                         false, vals != 0)) {
       if (lane == 0) {  // left to the summary walk from the root; reported
         atomicOr(err, kErrBadPtr);
         w[0] = dir_page_index(root);
@@ -492,7 +570,12 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
   const int lane = lane_id();
   const uint64_t n_ops = *n_ops_dev;
   const uint32_t ns = *u.ns_dev;
-  const uint64_t nwin = ((n_ops > ns ? n_ops : (uint64_t)ns) + kWave - 1) / kWave;
+  // the value form also follows the keys changed in place and the deletes
+  const bool vals = u.dir_vals && u.dir_form == kDirFormPairs;
+  const uint64_t n_del = vals && u.n_del ? *u.n_del : 0;
+  uint64_t n_all = n_ops > ns ? n_ops : (uint64_t)ns;
+  if (n_del > n_all) n_all = n_del;
+  const uint64_t nwin = (n_all + kWave - 1) / kWave;
   const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x / kWave);
   uint64_t work = 0;  // new keys + split pages this wave handled
   for (uint64_t win = (uint64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
@@ -504,8 +587,12 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
       const uint32_t o = oslot[i];
       placed = (o & kOpPlaced) && !(o >> 31);
       if (placed)
-        dir_note_new(u, u.op_key[i], (uint32_t)(ga_offset(pages[i]) >> 10), (int)(o & 63u));
+        dir_note_new(u, u.op_key[i], u.op_val[i], (uint32_t)(ga_offset(pages[i]) >> 10),
+                     (int)(o & 63u));
+      else if (vals)
+        dir_note_changed(u, u.op_key[i]);
     }
+    if (i < n_del) dir_note_changed(u, u.dk[i]);
     work += (uint64_t)__popcll(ballot(placed));
     // (b) the split segments of this window, one after another
     const uint64_t g = win * kWave + (uint64_t)lane;
@@ -519,10 +606,13 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
       uint64_t page = u.seg_page[gs];
       if (!ptr_ok(page, u.node, u.arena_bytes)) continue;
       // page 0 is the segment's page, unless that page became the root's
-      // internal page (the root grew: its left half is the leftmost)
-      {
+      // internal page (the root grew: its left half is the leftmost; a root
+      // leaf split into more pages than one internal page holds grew twice
+      // in the chunk, and the leaf is the leftmost's leftmost)
+      for (int lv = 0; lv < kMaxLevelOfTree && ptr_ok(page, u.node, u.arena_bytes); ++lv) {
         const Hdr h = parse_hdr(load_page_slice(u.arena, ga_offset(page)));
-        if (h.leftmost != 0) page = h.leftmost;
+        if (h.leftmost == 0) break;
+        page = h.leftmost;
       }
       for (uint32_t q = 0; q < P && ptr_ok(page, u.node, u.arena_bytes); ++q) {
         const uint8_t* pg = u.arena + ga_offset(page);
@@ -532,7 +622,7 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
         uint64_t k = 0, v = 0;
         uint32_t f = 0, r = 0;
         if ((uint32_t)lane < c && lane < kLeafCardinality) lane_entry(pg, lane, k, v, f, r);
-        dir_note_split_page(u, (uint32_t)(ga_offset(page) >> 10), h.lowest, h.highest, k,
+        dir_note_split_page(u, (uint32_t)(ga_offset(page) >> 10), h.lowest, h.highest, k, v,
                             c < (uint32_t)kLeafCardinality ? c : (uint32_t)kLeafCardinality);
         page = h.sibling;
         ++work;
@@ -564,7 +654,8 @@ void launch_dir_upkeep(const UpperArgs& u, const uint32_t* oslot, const uint64_t
 // the tree as it is: out[0] entries checked, out[1] leaf lists or split
 // points that differ, out[2] pair sets that differ, out[3] fingerprint
 // copies that miss a valid slot's fingerprint, out[4..7] the first bad
-// prefixes (+ 1; 0 = none)
+// prefixes (+ 1; 0 = none), out[8] value-form entries checked, out[9] those
+// whose inline keys or values differ from the tree's
 __global__ __launch_bounds__(256) void k_dir_verify(const uint8_t* __restrict__ arena,
                                                     uint64_t arena_bytes, uint16_t node,
                                                     uint64_t root, uint64_t dir_lo, uint32_t shift,
@@ -583,11 +674,13 @@ __global__ __launch_bounds__(256) void k_dir_verify(const uint8_t* __restrict__ 
     if (!pairs && !fp) continue;
     uint32_t v = 0, np = 0;
     const int form = pairs ? kDirFormPairs : kDirFormFp;
+    // a value-form entry (layout.h kDirVals) also against the keys and values
+    const bool vf = pairs && dir_vals_usable(cw);
     if (!dir_exact_entry(arena, arena_bytes, node, root, dir_lo, shift, p, hint, form, &v, &np,
-                         true))
+                         true, vf))
       continue;
     const uint32_t st = lane < 16 ? w[lane] : 0u;
-    bool bad_list = false, bad_pairs = false, bad_fp = false;
+    bool bad_list = false, bad_pairs = false, bad_fp = false, bad_vals = false;
     if (pairs) {
       const uint32_t vcw = rl32(v, 7);
       // leaf count, pages and split points
@@ -609,6 +702,23 @@ __global__ __launch_bounds__(256) void k_dir_verify(const uint8_t* __restrict__ 
       // (extra stored pairs -- deleted keys' -- only cost a read; a missing
       // one would hide a key)
       bad_pairs = miss || want > kDirPairMax;
+      if (vf) {
+        // the exact entry is in value form too, with the same number of
+        // keys, and every stored (pair, key, value) is one of its own
+        auto word = [&](uint32_t x, uint32_t q, int j) {  // word j of pair q's (key, value)
+          return rl32(x, q == 0 ? (j < 2 ? 2 + j : 3 + j) : 12 + j);
+        };
+        bad_vals = (vcw & kDirVals) == 0 || want != npst;
+        for (uint32_t x = 0; x < npst && !bad_vals; ++x) {
+          bool found = false;
+          for (uint32_t q = 0; q < want && q < kDirValMax; ++q) {
+            bool same = ((rl32(st, 8) >> (16 * x)) & 0xFFFFu) == ((rl32(v, 8) >> (16 * q)) & 0xFFFFu);
+            for (int j = 0; j < 4; ++j) same = same && word(st, x, j) == word(v, q, j);
+            found = found || same;
+          }
+          bad_vals = !found;
+        }
+      }
     } else {
       // the stored fingerprint copy must hold the fingerprint of every valid
       // slot whose key lies in the prefix, and name the exact leaf
@@ -630,7 +740,9 @@ __global__ __launch_bounds__(256) void k_dir_verify(const uint8_t* __restrict__ 
       if (bad_list) atomicAdd(out + 1, 1ull);
       if (bad_pairs) atomicAdd(out + 2, 1ull);
       if (bad_fp) atomicAdd(out + 3, 1ull);
-      if (bad_list || bad_pairs || bad_fp)
+      if (vf) atomicAdd(out + 8, 1ull);
+      if (bad_vals) atomicAdd(out + 9, 1ull);
+      if (bad_list || bad_pairs || bad_fp || bad_vals)
         for (int i = 0; i < 4; ++i)
           if (atomicCAS(out + 4 + i, 0ull, (unsigned long long)p + 1) == 0ull) break;
     }
@@ -647,7 +759,8 @@ void launch_dir_verify(const uint8_t* arena, uint64_t arena_bytes, uint16_t node
 void launch_dir_repair(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, uint64_t root,
                        uint64_t dir_lo, uint32_t shift, uint64_t n_ent, uint64_t* dir,
                        const uint32_t* hint, int form, const uint32_t* fix, uint32_t* fix_n,
-                       uint32_t par, uint32_t cap, uint64_t* lost, uint32_t* err, hipStream_t s) {
+                       uint32_t par, uint32_t cap, uint64_t* lost, uint32_t* err, hipStream_t s,
+                       int vals, uint64_t applied) {
   static unsigned nb = 0;
   if (!nb) {
     int cus = 0, dev = 0;
@@ -656,7 +769,8 @@ void launch_dir_repair(const uint8_t* arena, uint64_t arena_bytes, uint16_t node
     nb = (unsigned)(cus > 0 ? cus : 256) * 5;  // every resident wave slot at 5 per SIMD
   }
   hipLaunchKernelGGL(k_dir_repair, dim3(nb), dim3(256), 0, s, arena, arena_bytes, node, root,
-                     dir_lo, shift, n_ent, dir, hint, form, fix, fix_n, par, cap, lost, err);
+                     dir_lo, shift, n_ent, dir, hint, form, fix, fix_n, par, cap, lost, err, vals,
+                     applied);
 }
 
 }  // namespace dev

@@ -143,6 +143,7 @@ struct shm_tree {
   uint64_t dir_builds = 0;
   double dir_last_ms = -1.0, dir_total_ms = 0.0;
   bool dir_maint = false;    // the writers keep the entries current (dir_maint_enabled)
+  bool dir_vals = true;      // a pair-form build adds the value form (SHM_DIR_VALS, layout.h kDirVals)
   // the insert chunks' repair lists (dir_upkeep.h, k_dir_repair): prefix
   // indices, and a count per chunk parity
   uint32_t* dir_fix = nullptr;
@@ -637,6 +638,9 @@ int refresh_dir(shm_tree* t, hipStream_t s) {
   if (pairs)
     dev::launch_dir_pairs(t->arena, t->next_page, t->cfg.node_id, t->cfg.key_lo,
                           t->cfg.key_bits - bits, 1ull << bits, t->dir, s);
+  // the value form is only ever read from an exact directory
+  if (pairs && t->dir_vals && t->dir_maint)
+    dev::launch_dir_vals(t->arena, t->next_page, 1ull << bits, t->dir, s);
   HIP_OK(hipEventRecord(t->dir_ev[1], s));
   t->dir_ev_pending = true;
   ++t->dir_builds;
@@ -1041,6 +1045,10 @@ int insert_apply(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag,
     if (!t->dir_last_upkept) HIP_OK(hipMemsetAsync(t->dir_fix_n + u.par, 0, sizeof(uint32_t), s));
     u.dir_w = t->dir;
     u.dir_form = t->dir_pairs ? dev::kDirFormPairs : dev::kDirFormFp;
+    u.dir_vals = t->dir_pairs && t->dir_vals ? 1u : 0u;
+    // the upkeep reads this chunk's op buffers after k_upper: they are
+    // published free by k_dir_repair
+    u.pub_later = 1u;
     u.dir_fix = t->dir_fix;
     u.dir_fix_n = t->dir_fix_n;
     u.dir_fix_cap = t->dir_fix_cap;
@@ -1107,7 +1115,7 @@ int insert_apply(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag,
     dev::launch_dir_repair(t->arena, t->arena_bytes, t->cfg.node_id, t->root, u.dir_lo,
                            u.dir_shift, u.dir_n, t->dir, t->dir_hint, (int)u.dir_form, t->dir_fix,
                            t->dir_fix_n, u.par, t->dir_fix_cap, u.pub + dev::kPubDirLost,
-                           t->d_err, s);
+                           t->d_err, s, (int)u.dir_vals, (uint64_t)tag);
     DBG(s, "dir_repair");
   }
   HIP_OK(hipGetLastError());
@@ -1440,6 +1448,12 @@ int shm_tree_create(const shm_config* cfg, shm_tree** out) {
   if (t->cfg.key_bits == 0) t->cfg.key_bits = 64;
   if (t->cfg.key_bits == 64) t->cfg.key_lo = 0;
   t->dir_maint = dir_maint_enabled();
+  {
+    // SHM_DIR_VALS=0: builds and upkeep leave the entries in plain pair form
+    // (read per tree, so one process can run both)
+    const char* e = getenv("SHM_DIR_VALS");
+    t->dir_vals = !(e && e[0] == '0');
+  }
   auto fail = [&](int rc) {
     free_all(t);
     delete t;
@@ -2236,23 +2250,25 @@ int shm__dir_config(shm_tree* t, int maint, uint64_t mem_limit) {
 
 // diagnostics: every entry the walks trust against the tree as it is now
 // (k_dir_verify): out[0] checked, out[1..3] bad leaf lists / pair sets /
-// fingerprint copies, out[4..7] first bad prefixes + 1
+// fingerprint copies, out[4..7] first bad prefixes + 1, out[8..9] value-form
+// entries checked / wrong (kDirVerifyWords words)
 int shm__dir_verify(shm_tree* t, uint64_t* out) {
   if (!t || !out) return SHM_EINVAL;
   std::lock_guard<std::mutex> g(t->mu);
-  memset(out, 0, 8 * sizeof(uint64_t));
+  constexpr size_t kBytes = dev::kDirVerifyWords * sizeof(uint64_t);
+  memset(out, 0, kBytes);
   HIP_OK(hipDeviceSynchronize());
   if (!t->dir_valid) return SHM_OK;
   unsigned long long* d = nullptr;
-  if (dalloc(&d, 8)) return SHM_ENOMEM;
+  if (dalloc(&d, dev::kDirVerifyWords)) return SHM_ENOMEM;
   int rc = SHM_OK;
-  if (hipMemset(d, 0, 64) != hipSuccess) rc = SHM_EIO;
+  if (hipMemset(d, 0, kBytes) != hipSuccess) rc = SHM_EIO;
   if (!rc) {
     dev::launch_dir_verify(t->arena, t->arena_bytes, t->cfg.node_id, t->root, t->cfg.key_lo,
                            t->cfg.key_bits - t->dir_bits, 1ull << t->dir_bits, t->dir, t->dir_hint,
                            d, t->stream);
     if (hipStreamSynchronize(t->stream) != hipSuccess ||
-        hipMemcpy(out, d, 64, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(out, d, kBytes, hipMemcpyDeviceToHost) != hipSuccess)
       rc = SHM_EIO;
   }
   (void)hipFree(d);
