@@ -582,6 +582,22 @@ class Tree:
                 "first_bad": [x - 1 for x in out[4:8] if x],
                 "vals_checked": out[8], "bad_vals": out[9]}
 
+    def dir_dump(self):
+        """Test hook (shm__dir_dump): the raw directory as an (n, 16) uint32
+        array (one 64 B entry per row; n == 0 while no directory is valid)
+        and {"lo", "shift", "form"}: entry p covers the keys
+        [lo + (p << shift), lo + ((p + 1) << shift))."""
+        import numpy as np
+        info = (u64 * 4)()
+        _check(_hooks().shm__dir_dump(self.h, None, 0, info), "dir_dump")
+        ent = np.zeros((int(info[0]), 16), dtype=np.uint32)
+        if info[0]:
+            _check(_hooks().shm__dir_dump(self.h, ent.ctypes.data_as(vp), info[0], info),
+                   "dir_dump")
+            assert info[0] == ent.shape[0]
+        return ent, {"lo": int(info[1]), "shift": int(info[2]),
+                     "form": DIR_FORMS.get(int(info[3]) if info[0] else 0, str(info[3]))}
+
     def profile_read(self, reset=True):
         p = ShmProfile()
         _check(lib().shm_profile_read(self.h, ctypes.byref(p), 1 if reset else 0),
@@ -655,6 +671,7 @@ _HOOKS = [
     ("shm__dir_config", ctypes.c_int, [vp, ctypes.c_int, u64]),
     ("shm__shard_force_route", ctypes.c_int, [vp, ctypes.c_int]),
     ("shm__dir_verify", ctypes.c_int, [vp, ctypes.POINTER(u64)]),
+    ("shm__dir_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
 ]
 
 

@@ -143,6 +143,11 @@ __device__ __forceinline__ void dir_note_new(const UpperArgs& u, uint64_t k, uin
       dir_note_stale(u, w, dir_prefix(u, w));
       return;
     }
+    // A prefix that holds more keys than an entry has pairs (a build or a
+    // repair left its count above kDirPairMax: not usable, and no flag) stays
+    // as it is: counting on could only carry out of the count's byte, and
+    // listing it would rebuild it after every chunk that adds to it.
+    if (((cw >> 16) & 0xFFu) > kDirPairMax) return;
     const uint32_t pos = (atomicAdd(w + 7, 1u << 16) >> 16) & 0xFFu;
     // An entry built in value form (kDirVals; its leaf count <= 2 leaves
     // the inline words free) keeps the flag for good: the first kDirValMax
@@ -156,11 +161,15 @@ __device__ __forceinline__ void dir_note_new(const UpperArgs& u, uint64_t k, uin
       dir_note_stale(u, w, dir_prefix(u, w));
       return;
     }
-    if (pos < kDirPairMax)
-      reinterpret_cast<uint16_t*>(w + 8)[pos] =
-          (uint16_t)(key_fp(k) | (((uint32_t)s | ((uint32_t)j << 6)) << 8));
-    else
-      atomicOr(w + 7, kDirPairsBad);  // more keys than pairs: unusable (as a build leaves it)
+    // More pairs than the entry holds: some may be those of deleted keys
+    // (never removed), so the repair counts the prefix's valid keys again --
+    // at most kDirPairMax: a usable entry; more: the rule above.
+    if (pos >= kDirPairMax) {
+      dir_note_stale(u, w, dir_prefix(u, w));
+      return;
+    }
+    reinterpret_cast<uint16_t*>(w + 8)[pos] =
+        (uint16_t)(key_fp(k) | (((uint32_t)s | ((uint32_t)j << 6)) << 8));
     if ((cw & kDirVals) && pos < kDirValMax) dir_val_put(w, pos, k, v);
   } else if (u.dir_form == kDirFormFp && (cw & kDirFp)) {
     if (w[0] == pg)

@@ -2275,6 +2275,27 @@ int shm__dir_verify(shm_tree* t, uint64_t* out) {
   return rc;
 }
 
+// test hook: the raw directory, for a host-side check that shares no code
+// with the kernels (tests/dir_model.py).  Copies up to cap_entries 64 B
+// entries into buf (nullable: sizes only); info = {entries, dir_lo, shift,
+// form (shm_dir_stats' coding)}, entries 0 while no directory is valid.
+int shm__dir_dump(shm_tree* t, void* buf, uint64_t cap_entries, uint64_t* info) {
+  if (!t || !info) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  memset(info, 0, 4 * sizeof(uint64_t));
+  HIP_OK(hipDeviceSynchronize());
+  if (!t->dir_valid || !t->dir) return SHM_OK;
+  const uint64_t n = 1ull << t->dir_bits;
+  info[0] = n;
+  info[1] = t->cfg.key_lo;
+  info[2] = t->cfg.key_bits - t->dir_bits;
+  info[3] = t->dir_pairs ? 2u : 1u;
+  if (!buf) return SHM_OK;
+  if (cap_entries < n) return SHM_EINVAL;
+  HIP_OK(hipMemcpy(buf, t->dir, n * 8 * kDirWords, hipMemcpyDeviceToHost));
+  return SHM_OK;
+}
+
 int shm_profile_read(shm_tree* t, shm_profile_t* out, int reset) {
   if (!t || !out) return SHM_EINVAL;
   std::lock_guard<std::mutex> g(t->mu);

@@ -10,6 +10,9 @@ after splitting chunks, and the gets still answered from their entries.
 
 All GPU work runs in this one process.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
@@ -17,6 +20,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import dir_model  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
@@ -85,9 +91,13 @@ def loaded(n0, maint="always", arena=512 << 20, max_batch=1 << 18):
 def assert_dir_exact(t):
     """Every directory entry the walks trust names exactly what the tree
     holds (shm__dir_verify): leaf lists and split points, every key's pair,
-    every valid slot's fingerprint."""
+    every valid slot's fingerprint.  The device's self-check first, then the
+    host model on the raw dumps (tests/dir_model.py), which shares no code
+    with the kernels that write the entries."""
     v = t.dir_verify()
     assert v["bad_lists"] == 0 and v["bad_pairs"] == 0 and v["bad_fps"] == 0, v
+    bad, _ = dir_model.check_tree(t)
+    assert bad == [], bad
     return v
 
 

@@ -20,7 +20,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import dir_model  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
@@ -131,6 +133,10 @@ class Prefixes:
 def verify_clean(t):
     v = t.dir_verify()
     assert (v["bad_lists"], v["bad_pairs"], v["bad_fps"], v["bad_vals"]) == (0, 0, 0, 0), v
+    # and the host model on the raw dumps (tests/dir_model.py): the inline
+    # copies against the pages, by code the library does not share
+    bad, _ = dir_model.check_tree(t)
+    assert bad == [], bad
     return v
 
 
