@@ -223,6 +223,25 @@ int shm_range_query_batch_async(shm_tree *t, const uint64_t *from, const uint64_
 int shm_range_query_slots(shm_tree *t, const uint64_t *from, const uint64_t *to,
                           uint64_t n, uint64_t slot_cap, uint64_t *counts_out,
                           uint64_t *vals_out, uint64_t *status_dev, void *stream);
+/* Ordered scans with a count limit (YCSB-E's scan(start, count), lower_bound,
+ * cursor paging): scan i returns the first min(limit, matches) valid entries
+ * with from[i] <= key <= to[i] (to == NULL: no upper bound) in ascending
+ * unsigned key order, keys to keys_out[i * limit ...] and values to
+ * vals_out[i * limit ...]; counts_out[i] = the number of pairs written (at
+ * most limit; == limit means there may be more: the last key + 1 is the next
+ * from).  The rest of a scan's row is not written.  from[i] > to[i] and
+ * from[i] == kKeyMax give 0.  The traversal (the leaf holding `from`, then the
+ * sibling chain) and the validity rule (value != kValueNull, front == rear
+ * entry version) are Tree::range_query's (src/Tree.cpp:461-540,
+ * include/Tree.h:53-54); the order inside a leaf, the keys and the early stop
+ * are new.  Device pointers, no host synchronisation, any n; queued like
+ * shm_range_query_slots.  status_dev (device, 2 words, nullable): the call
+ * ORs its device error bits into status_dev[1] and leaves status_dev[0]
+ * alone.  n == 0 launches nothing; limit == 0, limit >= 2^31 or a null from /
+ * keys_out / vals_out / counts_out with n > 0 is SHM_EINVAL. */
+int shm_scan_batch(shm_tree *t, const uint64_t *from, const uint64_t *to, uint64_t n,
+                   uint64_t limit, uint64_t *keys_out, uint64_t *vals_out,
+                   uint64_t *counts_out, uint64_t *status_dev, void *stream);
 
 /* introspection / images (host pointers) ------------------------------------- */
 int shm_stats(shm_tree *t, shm_stats_t *out);

@@ -142,6 +142,7 @@ _SIGNATURES = [
     ("shm_range_query_batch_async", ctypes.c_int,
      [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]),
     ("shm_range_query_slots", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp]),
+    ("shm_scan_batch", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp]),
     ("shm_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmStats)]),
     ("shm_dump_image", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     ("shm_load_image", ctypes.c_int, [vp, vp, u64, u64]),
@@ -317,6 +318,32 @@ class PendingSlots:
         return c, v[mask]
 
 
+class PendingScan:
+    """Result of Tree.scan_batch: (counts, keys[n, limit], vals[n, limit])
+    once the scans have run.  Scan i's pairs, in ascending unsigned key order,
+    are keys[i, :counts[i]] and vals[i, :counts[i]] (int64 bit patterns of the
+    u64 words); the rest of its row is whatever the buffers held.
+    counts[i] == limit means there may be more: keys[i, limit - 1] + 1 is the
+    next `lo`."""
+
+    def __init__(self, tree, counts, keys, vals, limit, status, done):
+        n = counts.numel()
+        self.tree, self.counts, self.limit = tree, counts, limit
+        self.keys = keys.view(-1)[:n * limit].view(n, limit)
+        self.vals = vals.view(-1)[:n * limit].view(n, limit)
+        self.status, self.done = status, done
+
+    def check(self):
+        """Waits for the scans; a device error of the queued calls raises."""
+        if self.done is not None:
+            self.done.synchronize()
+        self.tree.synchronize()
+
+    def result(self):
+        self.check()
+        return self.counts, self.keys, self.vals
+
+
 class Tree:
     """One shard's B+tree in HBM (reference: class Tree, include/Tree.h:42)."""
 
@@ -473,6 +500,43 @@ class Tree:
                                            _ptr(vals), _ptr(status), sp),
                "range_query_slots")
         return PendingSlots(self, counts[:n], vals, slot_cap, status, _record_on(sp, dev))
+
+    def scan_batch(self, lo, limit, hi=None, stream=None, keys=None, vals=None, counts=None,
+                   status=None):
+        """Ordered scans with a count limit (shm_scan_batch): scan i is the
+        first `limit` valid entries with lo[i] <= key <= hi[i] (hi None: no
+        upper bound) in ascending unsigned key order, queued on `stream`
+        without a host wait.  Returns PendingScan: .result() gives (counts,
+        keys[n, limit], vals[n, limit]).  keys / vals / counts may be passed
+        in (reused buffers); status (2 device words, zeroed by the caller)
+        gets the device error bits ORed into status[1]."""
+        import torch
+        n = lo.numel()
+        dev = lo.device
+        if hi is not None:
+            assert hi.numel() == n
+        if counts is None:
+            counts = torch.empty(n, dtype=torch.int64, device=dev)
+        if keys is None:
+            keys = torch.empty((n, limit), dtype=torch.int64, device=dev)
+        if vals is None:
+            vals = torch.empty((n, limit), dtype=torch.int64, device=dev)
+        assert keys.numel() >= n * limit and vals.numel() >= n * limit and counts.numel() >= n
+        sp = _stream_ptr(stream)
+        _check(lib().shm_scan_batch(self.h, _ptr(lo), _ptr(hi), n, limit, _ptr(keys), _ptr(vals),
+                                    _ptr(counts), _ptr(status), sp), "scan_batch")
+        return PendingScan(self, counts[:n], keys, vals, limit, status, _record_on(sp, dev))
+
+    def lower_bound_batch(self, keys, stream=None):
+        """The first stored key >= keys[i] (a scan with limit 1): (found,
+        key, value) tensors of n; key and value are 0 where found is False
+        (nothing at or after keys[i]).  Waits for the result."""
+        import torch
+        n = keys.numel()
+        k = torch.zeros(n, dtype=torch.int64, device=keys.device)
+        v = torch.zeros(n, dtype=torch.int64, device=keys.device)
+        c, k, v = self.scan_batch(keys, 1, stream=stream, keys=k, vals=v).result()
+        return c != 0, k.view(-1), v.view(-1)
 
     # -- reference single-op API (Tree.h:47-54) -------------------------------
     def _dev(self, name, n):

@@ -7,6 +7,7 @@
 //   bool search(const Key&, Value&, ...)        search(k, v[, cxt, coro_id])
 //   void del(const Key&, ...)                   del(k[, cxt, coro_id])
 //   uint64_t range_query(from, to, Value* buf)  range_query(from, to, buf[, cxt, coro_id])
+//   (new) ordered scan with a count limit       scan(from, limit, keys, vals)
 //   void print_and_check_tree(...)              print_and_check_tree([cxt, coro_id])
 //   void lock_bench(const Key&, ...)            lock_bench(k[, cxt, coro_id])
 //   void index_cache_statistics()               index_cache_statistics() (the leaf directory's)
@@ -129,6 +130,32 @@ class Tree {
     (void)hipFree(d_out);
     (void)hipFree(d_off);
     check(s, "range_query");
+    return cnt;
+  }
+
+  // The first `limit` valid entries with key >= from in ascending key order
+  // (shm_scan_batch; the traversal of Tree::range_query, Tree.cpp:461-540):
+  // keys[i] / vals[i] for i < the returned count (<= limit; == limit: there
+  // may be more, keys[limit - 1] + 1 is the next from).  Host pointers.
+  uint64_t scan(const Key& from, uint64_t limit, Key* keys, Value* vals) {
+    uint64_t *d_cnt = d_vals_, *d_out = nullptr;
+    if (limit == 0 || limit >= (1ull << 31)) throw Error(SHM_EINVAL, "scan limit");
+    if (hipMemcpy(d_keys_, &from, sizeof(from), hipMemcpyHostToDevice) != hipSuccess)
+      throw Error(SHM_EIO, "scan stage");
+    if (hipMalloc(&d_out, 2 * limit * sizeof(uint64_t)) != hipSuccess)
+      throw Error(SHM_ENOMEM, "scan buffers");
+    int s = shm_scan_batch(t_, d_keys_, nullptr, 1, limit, d_out, d_out + limit, d_cnt, nullptr,
+                           nullptr);
+    uint64_t cnt = 0;
+    if (s == SHM_OK && hipMemcpy(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)
+      s = SHM_EIO;
+    if (s == SHM_OK && cnt &&
+        (hipMemcpy(keys, d_out, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+         hipMemcpy(vals, d_out + limit, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost) !=
+             hipSuccess))
+      s = SHM_EIO;
+    (void)hipFree(d_out);
+    check(s, "scan");
     return cnt;
   }
 

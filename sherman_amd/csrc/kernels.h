@@ -1,6 +1,6 @@
 // kernels.h — launch interface between the host runtime (tree.cpp) and the
 // HIP kernels (get.hip, locate.hip, isort.hip, partition.hip, upsert.hip,
-// insert.hip, leafdir.hip, range.hip, util.hip).  Host-only types; no torch.
+// insert.hip, leafdir.hip, range.hip, scan.hip, util.hip).  Host-only types; no torch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -599,6 +599,35 @@ struct RangeArgs {
 void launch_range(const RangeArgs& a, hipStream_t s);
 // x[i] += c for i < n
 void launch_add_u64(uint64_t* x, uint64_t n, uint64_t c, hipStream_t s);
+
+// ---- ordered scans with a count limit (scan.hip) ----------------------------------
+struct ScanArgs {
+  const uint8_t* arena;
+  uint64_t arena_bytes;
+  uint16_t node;
+  uint64_t root;
+  const uint64_t* from;
+  const uint64_t* to;  // nullable: no upper bound
+  uint64_t n;
+  uint32_t limit;      // 1 .. 2^31 - 1 pairs per scan
+  // scan i's first min(limit, matches) pairs in ascending key order at
+  // keys / vals [i * limit ...], their number in counts[i]; the rest of the
+  // row is not written
+  uint64_t* keys;
+  uint64_t* vals;
+  uint64_t* counts;
+  uint32_t* err;
+  // leaf directory (nullable), as in WalkArgs
+  const uint64_t* dir;
+  uint64_t dir_lo;
+  uint64_t dir_n;
+  uint32_t dir_shift;
+  // per-page occupancy bound (nullable), as in RangeArgs
+  const uint8_t* leaf_hw;
+  // nullable: status[1] |= this launch's error bits (status[0] is left alone)
+  uint64_t* status;
+};
+void launch_scan(const ScanArgs& a, hipStream_t s);
 
 // ---- host read-backs (range.hip) ------------------------------------------------
 // dst[i] = src[i] for i < nw (<= 256, dst in mapped host memory), then a

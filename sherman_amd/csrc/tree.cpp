@@ -1954,6 +1954,49 @@ int shm_range_query_slots(shm_tree* t, const uint64_t* from, const uint64_t* to,
   return range_launch(t, s, a);
 }
 
+int shm_scan_batch(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n,
+                   uint64_t limit, uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out,
+                   uint64_t* status_dev, void* stream) {
+  // the arguments first: a rejected call uses neither the handle nor the GPU
+  if (limit == 0 || limit >= (1ull << 31)) return SHM_EINVAL;
+  if (n && (!from || !keys_out || !vals_out || !counts_out)) return SHM_EINVAL;
+  if (!t) return SHM_EINVAL;
+  if (n == 0) return SHM_OK;
+  std::lock_guard<std::mutex> g(t->mu);
+  hipStream_t s = pick(stream);
+  Order ord(t, s, true);  // the directory refresh
+  if (ord.rc) return ord.rc;
+  if (const int rc = range_prepare(t, s)) return rc;
+  dev::ScanArgs a{};
+  a.arena = t->arena;
+  a.arena_bytes = t->arena_bytes;
+  a.node = t->cfg.node_id;
+  a.root = t->root;
+  a.from = from;
+  a.to = to;
+  a.n = n;
+  a.limit = (uint32_t)limit;
+  a.keys = keys_out;
+  a.vals = vals_out;
+  a.counts = counts_out;
+  a.err = t->d_err;
+  a.leaf_hw = t->leaf_hw;
+  set_dir(t, &a.dir, &a.dir_lo, &a.dir_shift, &a.dir_n);
+  a.status = status_dev;
+  t->err_pending = true;
+  shm_tree::ProfRec pr{};
+  if (t->prof_on) {
+    if (const int rc = prof_begin(t, s, shm_tree::kProfRange, n, 2, pr)) return rc;
+  }
+  dev::launch_scan(a, s);
+  HIP_OK(hipGetLastError());
+  if (t->prof_on) {
+    HIP_OK(hipEventRecord(pr.e[1], s));
+    t->prof_pending.push_back(pr);
+  }
+  return SHM_OK;
+}
+
 // Library-internal, not part of include/sherman_amd.h (shard.cpp): a routed
 // insert's received slots, kKeyMax padding skipped, queued as
 // shm_insert_batch_async (n <= max_batch: one chunk)
