@@ -662,6 +662,30 @@ class Tree:
         return ent, {"lo": int(info[1]), "shift": int(info[2]),
                      "form": DIR_FORMS.get(int(info[3]) if info[0] else 0, str(info[3]))}
 
+    def vt_stats(self):
+        """Test hook (shm__vt_stats): the key-value bucket table a read
+        phase's gets read first: buckets, bytes, dead buckets, the stored keys
+        that ended in dead buckets at the last build, the stored keys then,
+        and whether gets and chunks use it (all 0 without a table)."""
+        out = (u64 * 6)()
+        _check(_hooks().shm__vt_stats(self.h, out), "vt_stats")
+        return {"buckets": out[0], "bytes": out[1], "dead_buckets": out[2],
+                "dead_keys_at_build": out[3], "keys_at_build": out[4], "trusted": bool(out[5])}
+
+    def vt_dump(self):
+        """Test hook (shm__vt_dump): the raw bucket table as an (n, 16)
+        uint64 array (one 128 B bucket per row: key, value of slots 0..7;
+        n == 0 without a table) and {"lo", "shift", "trusted"}: bucket b
+        covers the keys [lo + (b << shift), lo + ((b + 1) << shift))."""
+        import numpy as np
+        info = (u64 * 4)()
+        _check(_hooks().shm__vt_dump(self.h, None, 0, info), "vt_dump")
+        b = np.zeros((int(info[0]), 16), dtype=np.uint64)
+        if info[0]:
+            _check(_hooks().shm__vt_dump(self.h, b.ctypes.data_as(vp), info[0], info), "vt_dump")
+            assert info[0] == b.shape[0]
+        return b, {"lo": int(info[1]), "shift": int(info[2]), "trusted": bool(info[3])}
+
     def profile_read(self, reset=True):
         p = ShmProfile()
         _check(lib().shm_profile_read(self.h, ctypes.byref(p), 1 if reset else 0),
@@ -736,13 +760,19 @@ _HOOKS = [
     ("shm__shard_force_route", ctypes.c_int, [vp, ctypes.c_int]),
     ("shm__dir_verify", ctypes.c_int, [vp, ctypes.POINTER(u64)]),
     ("shm__dir_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
+    ("shm__vt_stats", ctypes.c_int, [vp, ctypes.POINTER(u64)]),
+    ("shm__vt_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
 ]
 
 
 def _hooks():
     L = lib()
     for name, res, args in _HOOKS:
-        f = getattr(L, name)
+        f = getattr(L, name, None)
+        if f is None and os.environ.get("SHM_LIB_PATH"):
+            continue  # an older build under SHM_LIB_PATH (A/B of builds) lacks newer hooks
+        if f is None:
+            raise AttributeError(f"{LIB_PATH} lacks the hook {name}")
         f.restype, f.argtypes = res, args
     return L
 

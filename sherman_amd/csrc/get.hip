@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "lds_dma.h"
 #include "leaf_chunk.h"
+#include "valtab.h"
 
 namespace shm {
 namespace dev {
@@ -331,7 +332,9 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
 // (80 VGPRs: C2 +2 % against 5 then); with the pair form and the shared
 // rounds the cap spilled 28-48 B per lane into scratch on the candidate
 // rounds: same box C2 18623 / 18631 and C3 12750 / 12903 at 6 waves against
-// 19572 / 19611 and 14828 / 14986 at 5.
+// 19572 / 19611 and 14828 / 14986 at 5.  With the bucket table's probe in
+// front (valtab.h: 32 more registers live until the probe ends) still 95
+// VGPRs, no scratch, 5 waves (PCHK, which has no probe: 96).
 // PCHK (SHM_FLAG_PAGE_CHECK): the page-level version check on the fast
 // path too -- a hit read from a page's entry also reads that page's
 // front_version (byte 8) and rear_version (byte 1016) and reports a
@@ -363,7 +366,24 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k
     uint64_t ptr = a.root;
     uint64_t alt = 0;  // a tie's safe start (dir_start_e)
     bool done = false;  // val is the answer
-    if (a.dir) {
+    // the bucket table (valtab.h) first: one 128 B line holds every key of
+    // k's bucket, so a live bucket answers the get -- the key's value, or
+    // absent -- with this one request; a dead bucket (more than 8 keys) goes
+    // on below as before.  The 32 bucket registers are dead past this block.
+    if (!PCHK && a.vt) {
+      uint64_t b;
+      if (vt_bucket_of(a.vt_lo, a.vt_shift, a.vt_n, k, &b)) {
+        const u32x4* bp = reinterpret_cast<const u32x4*>(a.vt + kVtBucketWords * b);
+        u32x4 w[kVtSlots];
+#pragma unroll
+        for (int j = 0; j < kVtSlots; ++j) w[j] = bp[j];
+        const int r = vt_probe(w, k, &val);
+        hit = r >= 0;
+        done = r != kVtDead;
+      }
+    }
+    if (done) {
+    } else if (a.dir) {
       u32x4 e[4];
       bool fpform;
       ptr = dir_start_e(a.dir, a.dir_lo, a.dir_shift, a.dir_n, a.node, k, ptr, e, fpform, &alt);

@@ -10,6 +10,12 @@
 namespace shm {
 namespace dev {
 
+// the key-value bucket table's format (valtab.h): 8 slots of (key, value) per
+// 128 B bucket; the build's counter words
+constexpr int kVtSlots = 8;
+constexpr int kVtBucketWords = 2 * kVtSlots;  // u64 words: 128 B
+constexpr int kVtCtrWords = 4;
+
 struct WalkArgs {
   const uint8_t* arena;
   uint64_t arena_bytes;
@@ -79,6 +85,14 @@ struct WalkArgs {
   // clk[b] = block b's start, clk[gridDim.x + w] = wave w's end (after its
   // result stores are issued); the host takes last end - first start
   uint64_t* clk;
+  // GET (k_get_sum without page_check), nullable: the key-value bucket table
+  // (valtab.h), read before the directory: vt_n buckets of 16 u64, bucket b
+  // covers keys [vt_lo + (b << vt_shift), ... + 2^vt_shift).  Set only while
+  // the table is trusted (tree.cpp vt_trusted); never in LOCATE or the scans
+  const uint64_t* vt;
+  uint64_t vt_lo;
+  uint64_t vt_n;
+  uint32_t vt_shift;
 };
 // k_get_sum's index statistics (shm_index_stats)
 enum IdxStat {
@@ -135,6 +149,11 @@ void launch_dir_pairs(const uint8_t* arena, uint64_t n_pages, uint16_t node, uin
 // the value form after the pairs (layout.h kDirVals): one thread per entry
 void launch_dir_vals(const uint8_t* arena, uint64_t n_pages, uint64_t n_ent, uint64_t* dir,
                      hipStream_t s);
+// the key-value bucket table (valtab.h) from the leaves, after a zero fill:
+// one wave per page of [1, n_pages); ctr (zeroed by the caller) = {dead
+// buckets, stored keys that ended in dead buckets, stored keys}
+void launch_vt_build(const uint8_t* arena, uint64_t n_pages, uint64_t lo, uint32_t shift,
+                     uint64_t n_buckets, uint64_t* vt, uint64_t* ctr, hipStream_t s);
 // rebuild the entries an insert chunk listed (fix[0 .. fix_n[par]), at most
 // cap) from the tree, in form `form` (kDirForm*); zeroes fix_n[par ^ 1]; the
 // repairs past cap are added to *lost (host memory, nullable)
@@ -372,6 +391,14 @@ struct UpperArgs {
   // free) is then published by k_dir_repair, which runs after the upkeep,
   // and not by the kernel that completes the chunk
   uint32_t pub_later;
+  // nullable: the key-value bucket table (valtab.h), kept by k_dir_upkeep in
+  // the same launch: every upsert of the chunk stored, every delete removed;
+  // vt_ctr[0] counts the buckets the chunk's keys overflowed
+  uint64_t* vt;
+  uint64_t vt_lo;
+  uint64_t vt_n;
+  uint32_t vt_shift;
+  uint64_t* vt_ctr;
 };
 constexpr int kUpperStamps = 32;
 // diagnostic clock words: k_upper's, then k_bin_unique's 8 phases x kCoarse bins

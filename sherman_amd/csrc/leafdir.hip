@@ -23,6 +23,7 @@
 #include "device_common.h"
 #include "dir_upkeep.h"
 #include "kernels.h"
+#include "valtab.h"
 
 namespace shm {
 namespace dev {
@@ -309,6 +310,55 @@ void launch_dir_vals(const uint8_t* arena, uint64_t n_pages, uint64_t n_ent, uin
                      n_pages, n_ent, dir);
 }
 
+// The key-value bucket table (valtab.h) of a read phase's build, after the
+// host's zero fill: one wave per page, as k_dir_pairs; every valid entry of a
+// leaf (value != 0, f == r: the entries a get can find) is stored by
+// vt_upsert.  ctr = {dead buckets, stored keys that ended in dead buckets,
+// stored keys}: a bucket dies once, by the lane whose exchange set the marker
+// over 8 claimed slots (8 keys and its own), and every other key of a dead
+// bucket counts itself, so the counts are exact.
+__global__ __launch_bounds__(256) void k_vt_build(const uint8_t* __restrict__ arena,
+                                                  uint64_t n_pages, uint64_t lo, uint32_t shift,
+                                                  uint64_t n_b, uint64_t* vt, uint64_t* ctr) {
+  const int lane = lane_id();
+  const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x / kWave);
+  uint32_t killed = 0, in_dead = 0, stored = 0;
+  for (uint64_t pi = 1 + (uint64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
+       pi < n_pages; pi += nw) {
+    const uint8_t* pg = arena + (pi << 10);
+    if (pg[kOffLevel] != 0 || pg64_b1(pg, 2) != 0) continue;  // a leaf (no leftmost)
+    if (lane >= kLeafCardinality) continue;
+    uint64_t k, v, b;
+    uint32_t f, r;
+    lane_entry(pg, lane, k, v, f, r);
+    if (v == kValueNull || ((f ^ r) & 0xF) != 0) continue;
+    if (!vt_bucket_of(lo, shift, n_b, k, &b)) continue;
+    ++stored;
+    const VtPut p = vt_upsert(vt + kVtBucketWords * b, k, v);
+    if (p == kVtKilled) {
+      ++killed;
+      in_dead += kVtSlots + 1;
+    } else if (p == kVtInDead) {
+      ++in_dead;
+    }
+  }
+  const uint32_t c[3] = {killed, in_dead, stored};
+  for (int j = 0; j < 3; ++j) {
+    uint32_t x = c[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o);
+    if (lane == 0 && x)
+      atomicAdd(reinterpret_cast<unsigned long long*>(ctr + j), (unsigned long long)x);
+  }
+}
+
+void launch_vt_build(const uint8_t* arena, uint64_t n_pages, uint64_t lo, uint32_t shift,
+                     uint64_t n_buckets, uint64_t* vt, uint64_t* ctr, hipStream_t s) {
+  if (n_pages <= 1 || !n_buckets) return;
+  hipLaunchKernelGGL(k_vt_build, dim3(2048), dim3(256), 0, s, arena, n_pages, lo, shift,
+                     n_buckets, vt, ctr);
+}
+
 // The exact entry of prefix p as a build would write it (one wave): word
 // `lane` of the 64 B entry in *v for lanes < 16; false when the walk failed
 // (a bad pointer).  In the pair form *np_out = the pair count.
@@ -572,7 +622,7 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
   const uint32_t ns = *u.ns_dev;
   // the value form also follows the keys changed in place and the deletes
   const bool vals = u.dir_vals && u.dir_form == kDirFormPairs;
-  const uint64_t n_del = vals && u.n_del ? *u.n_del : 0;
+  const uint64_t n_del = (vals || u.vt) && u.n_del ? *u.n_del : 0;
   uint64_t n_all = n_ops > ns ? n_ops : (uint64_t)ns;
   if (n_del > n_all) n_all = n_del;
   const uint64_t nwin = (n_all + kWave - 1) / kWave;
@@ -592,7 +642,25 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
       else if (vals)
         dir_note_changed(u, u.op_key[i]);
     }
-    if (i < n_del) dir_note_changed(u, u.dk[i]);
+    if (i < n_del && vals) dir_note_changed(u, u.dk[i]);
+    // the bucket table follows every op of the chunk, whatever the tree did
+    // with it (placed, updated in place, split): it is independent of leaves
+    if (u.vt) {
+      uint64_t b;
+      uint32_t killed = 0;
+      if (i < n_ops && vt_bucket_of(u.vt_lo, u.vt_shift, u.vt_n, u.op_key[i], &b)) {
+        const uint64_t v = u.op_val[i];
+        if (v == kValueNull)
+          vt_delete(u.vt + kVtBucketWords * b, u.op_key[i]);
+        else
+          killed = vt_upsert(u.vt + kVtBucketWords * b, u.op_key[i], v) == kVtKilled ? 1u : 0u;
+      }
+      if (i < n_del && vt_bucket_of(u.vt_lo, u.vt_shift, u.vt_n, u.dk[i], &b))
+        vt_delete(u.vt + kVtBucketWords * b, u.dk[i]);
+      const uint32_t nk = (uint32_t)__popcll(ballot(killed != 0));
+      if (nk && lane == 0)
+        atomicAdd(reinterpret_cast<unsigned long long*>(u.vt_ctr), (unsigned long long)nk);
+    }
     work += (uint64_t)__popcll(ballot(placed));
     // (b) the split segments of this window, one after another
     const uint64_t g = win * kWave + (uint64_t)lane;

@@ -38,6 +38,8 @@ constexpr uint32_t kRangeStage = 160;      // staged values per range scan
 constexpr uint64_t kRangeStageBytes = 256ull << 20;  // staging budget
 constexpr uint32_t kFlagWord = 512;        // read-back sequence word: byte 2048 of h_pin
 constexpr uint32_t kPubWord = 768;         // superblock mirror: u64 words 384.. of h_pin
+constexpr uint32_t kVtWord = 896;          // bucket table build counts: u64 words 448..450 of h_pin
+constexpr uint32_t kVtFlagWord = 904;      // ... and their sequence word
 constexpr int kAppWaitMs = 5;              // insert_order's host wait before an event fallback
 // polls of an earlier segmentation tile's word before a tile counts that
 // tile's staged heads itself (seg_tile.h; ~1 ms, far past a placed tile's
@@ -158,6 +160,21 @@ struct shm_tree {
   bool dir_maint_always = false;  // shm__dir_config maint 2: every chunk keeps it (tests)
   bool dir_last_upkept = false;   // the previous chunk kept the directory
   double dir_debt_ps = 0.0;  // gets' estimated extra cost on shared prefixes since the build
+  // the key-value bucket table (valtab.h): 2^vt_bits buckets of 128 B, built
+  // with a read phase's value-form directory (refresh_dir), kept by the same
+  // chunks that keep the directory, trusted exactly while dir_exact holds
+  uint64_t* vt = nullptr;
+  uint64_t vt_bytes = 0;       // the allocation
+  uint32_t vt_bits = 0;
+  bool vt_valid = false;       // built for the directory as it is, not dropped
+  bool vt_on = true;           // SHM_VALTAB
+  uint64_t vt_max_bytes = 8ull << 30;  // SHM_VALTAB_MAX_BYTES
+  uint32_t vt_bits_failed = 64;  // an allocation this large failed: not asked again
+  uint32_t vt_drop_bits = 0;   // the table was dropped at this size (too many keys in dead buckets)
+  uint64_t* vt_ctr = nullptr;  // device: {dead buckets, keys in dead buckets, keys} (kVtCtrWords)
+  uint32_t vt_seq = 0;         // the last build's sequence number in the host words
+  bool vt_pending = false;     // its counts were not read yet (vt_poll)
+  uint64_t vt_dead_keys = 0, vt_keys = 0;  // at the last build
   // LDS replica of the top of the tree (SHM_FLAG_TOP_LDS without the
   // directory; launch_top), rebuilt with the same staleness rule
   uint64_t* top_keys = nullptr;
@@ -603,13 +620,117 @@ int dir_alloc(shm_tree* t, uint32_t bits, hipStream_t s) {
   }
 }
 
-int refresh_dir(shm_tree* t, hipStream_t s) {
-  if (const int rc = dir_poll(t, false)) return rc;
-  if (!dir_stale(t)) return SHM_OK;
-  static const bool trace = [] {
+// The bucket table pays only while most gets end at their bucket: with p the
+// share of stored keys in live buckets and R ~ 1.7 the directory path's
+// requests per get, p + (1 - p)(1 + R) < R needs p > 1 / R ~ 0.6.  Below
+// kVtMinLive (clustered or dense key sets: every get would pay one more
+// request for nothing) the table is dropped.
+constexpr double kVtMinLive = 0.75;
+
+// SHM_TRACE_DIR=1: the directory's and the table's builds and drops on stderr
+bool dir_trace() {
+  static const bool on = [] {
     const char* e = getenv("SHM_TRACE_DIR");
     return e && e[0] == '1';
   }();
+  return on;
+}
+
+void vt_free(shm_tree* t) {
+  if (t->vt) (void)hipFree(t->vt);
+  t->vt = nullptr;
+  t->vt_bytes = 0;
+  t->vt_valid = false;
+}
+
+// the last table build's counts once they arrived in the host words (wait:
+// block for them); applies the drop rule
+int vt_poll(shm_tree* t, bool wait) {
+  if (!t->vt_pending) return SHM_OK;
+  const uint32_t* flag = reinterpret_cast<const uint32_t*>(t->h_pin) + kVtFlagWord;
+  if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != t->vt_seq) {
+    if (!wait) return SHM_OK;
+    HIP_OK(hipDeviceSynchronize());
+    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != t->vt_seq) return SHM_EIO;
+  }
+  const volatile uint64_t* c = reinterpret_cast<const volatile uint64_t*>(t->h_pin) + kVtWord / 2;
+  t->vt_dead_keys = c[1];
+  t->vt_keys = c[2];
+  t->vt_pending = false;
+  if (dir_trace())
+    fprintf(stderr, "sherman_amd: bucket table: 2^%u buckets, %llu of %llu stored keys in dead "
+            "buckets\n", t->vt_bits, (unsigned long long)t->vt_dead_keys,
+            (unsigned long long)t->vt_keys);
+  if (t->vt_valid && (double)(t->vt_keys - t->vt_dead_keys) < kVtMinLive * (double)t->vt_keys) {
+    // searches on other streams may still read it
+    HIP_OK(hipDeviceSynchronize());
+    t->vt_drop_bits = t->vt_bits;
+    vt_free(t);
+  }
+  return SHM_OK;
+}
+
+// the table is read by the gets and kept by the chunks
+bool vt_trusted(const shm_tree* t) {
+  return t->vt && t->vt_valid && t->dir_valid && t->dir_exact && t->dir_pairs;
+}
+
+// the table of a read phase's build (inside its timing events): half as many
+// buckets as the directory has entries, all or nothing -- a smaller table's
+// buckets would all overflow
+int vt_build(shm_tree* t, hipStream_t s, bool want) {
+  t->vt_valid = false;
+  t->vt_pending = false;
+  // no table for this build: the old one goes (its last readers are ordered
+  // before s), so its bytes do not outlive the read phase that used them
+  auto none = [&]() -> int {
+    if (t->vt) {
+      HIP_OK(hipStreamSynchronize(s));
+      vt_free(t);
+    }
+    return SHM_OK;
+  };
+  if (!want || !t->vt_on || t->dir_bits < 2) return none();
+  const uint32_t bits = t->dir_bits - 1;
+  if (bits == t->vt_drop_bits) return none();  // dropped at this size: not again until the tree doubled
+  const uint64_t bytes = (8ull * dev::kVtBucketWords) << bits;
+  const uint64_t dir_bytes = (1ull << t->dir_cap_bits) * (8 * kDirWords + 8);
+  bool ok = bytes <= t->vt_max_bytes && bits < t->vt_bits_failed &&
+            !(t->dir_mem_limit && dir_bytes + bytes > t->dir_mem_limit);
+  if (ok && t->vt_bytes != bytes) {
+    if (t->vt) {  // the old table's last readers are ordered before s
+      HIP_OK(hipStreamSynchronize(s));
+      vt_free(t);
+    }
+    if (hipMalloc((void**)&t->vt, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      t->vt = nullptr;
+      t->vt_bits_failed = bits;
+      ok = false;
+    } else {
+      t->vt_bytes = bytes;
+    }
+  }
+  if (!ok) return none();
+  if (!t->vt_ctr && dalloc(&t->vt_ctr, dev::kVtCtrWords)) return SHM_ENOMEM;
+  t->vt_bits = bits;
+  HIP_OK(hipMemsetAsync(t->vt, 0, bytes, s));
+  HIP_OK(hipMemsetAsync(t->vt_ctr, 0, 8 * dev::kVtCtrWords, s));
+  dev::launch_vt_build(t->arena, t->next_page, t->cfg.key_lo, t->cfg.key_bits - bits, 1ull << bits,
+                       t->vt, t->vt_ctr, s);
+  // the counts into the host words (the drop rule reads them lazily)
+  t->vt_seq = t->vt_seq + 1 ? t->vt_seq + 1 : 1;
+  dev::launch_readback(t->h_pin_dev + kVtWord, reinterpret_cast<const uint32_t*>(t->vt_ctr), 6,
+                       t->h_pin_dev + kVtFlagWord, t->vt_seq, 0, s);
+  t->vt_valid = true;
+  t->vt_pending = true;
+  return SHM_OK;
+}
+
+int refresh_dir(shm_tree* t, hipStream_t s) {
+  if (const int rc = dir_poll(t, false)) return rc;
+  if (!dir_stale(t)) return SHM_OK;
+  const bool trace = dir_trace();
   if (trace)
     fprintf(stderr, "sherman_amd: leaf directory rebuild: pages %llu (last build %llu), %u reads "
             "since the last insert, debt %.1f us\n", (unsigned long long)t->next_page,
@@ -618,6 +739,7 @@ int refresh_dir(shm_tree* t, hipStream_t s) {
   if (const int rc = dir_alloc(t, bits, s)) return rc;
   if (t->dir_off) {
     t->dir_valid = false;
+    t->vt_valid = false;
     return SHM_OK;
   }
   if (bits > t->dir_cap_bits) bits = t->dir_cap_bits;
@@ -641,6 +763,12 @@ int refresh_dir(shm_tree* t, hipStream_t s) {
   // the value form is only ever read from an exact directory
   if (pairs && t->dir_vals && t->dir_maint)
     dev::launch_dir_vals(t->arena, t->next_page, 1ull << bits, t->dir, s);
+  // ... and so is the bucket table, built with it
+  // (a read phase's build only: a write phase that went quiet builds pairs
+  // too, but its gets share the device with chunks that would each pay the
+  // table's upkeep)
+  if (const int rc = vt_build(t, s, pairs && t->dir_vals && t->dir_maint && read_phase(t)))
+    return rc;
   HIP_OK(hipEventRecord(t->dir_ev[1], s));
   t->dir_ev_pending = true;
   ++t->dir_builds;
@@ -968,6 +1096,9 @@ int insert_apply(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag,
   }
   const bool upkeep = t->dir_maint && t->dir_exact && t->dir_valid &&
                       ((searched && t->dir_idle_upkeeps < kIdleUpkeeps) || t->dir_maint_always);
+  if (!upkeep && t->dir_exact && dir_trace())
+    fprintf(stderr, "sherman_amd: chunk %u not kept: the directory is no longer exact (searched %d, "
+            "idle upkeeps %u)\n", tag, (int)searched, t->dir_idle_upkeeps);
   if (!upkeep) t->dir_exact = false;
   // the byte marks repeat every 255 chunks: clear them when they wrap, so
   // no page still carries this chunk's mark from 255 chunks ago
@@ -1052,6 +1183,13 @@ int insert_apply(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag,
     u.dir_fix = t->dir_fix;
     u.dir_fix_n = t->dir_fix_n;
     u.dir_fix_cap = t->dir_fix_cap;
+    if (vt_trusted(t)) {  // the same launch keeps the bucket table
+      u.vt = t->vt;
+      u.vt_lo = t->cfg.key_lo;
+      u.vt_shift = t->cfg.key_bits - t->vt_bits;
+      u.vt_n = 1ull << t->vt_bits;
+      u.vt_ctr = t->vt_ctr;
+    }
   }
   u.stamps = t->stamps;
   u.force_abort = (t->force_flags & 1u) ? 1u : 0u;
@@ -1213,7 +1351,7 @@ void free_all(shm_tree* t) {
   F(t->uk); F(t->uv); F(t->dk); F(t->pages); F(t->seg_lb); F(t->bsum64);
   F(t->seg_start); F(t->seg_end); F(t->seg_page); F(t->seg_T); F(t->seg_P); F(t->seg_np);
   F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->oslot); F(t->pnew);
-  F(t->ctl); F(t->leaf_rd); F(t->dir_fix); F(t->dir_fix_n);
+  F(t->ctl); F(t->leaf_rd); F(t->dir_fix); F(t->dir_fix_n); F(t->vt); F(t->vt_ctr);
   for (int i = 0; i < 2; ++i) { F(t->sep_key[i]); F(t->sep_ptr[i]); F(t->ipage[i]); }
   F(t->h_end); F(t->h_T); F(t->h_P); F(t->h_ver); F(t->h_lk);
   F(t->d_head); F(t->d_base); F(t->int_rd);
@@ -1453,6 +1591,10 @@ int shm_tree_create(const shm_config* cfg, shm_tree** out) {
     // (read per tree, so one process can run both)
     const char* e = getenv("SHM_DIR_VALS");
     t->dir_vals = !(e && e[0] == '0');
+    // SHM_VALTAB=0: no bucket table (A/B); SHM_VALTAB_MAX_BYTES: its byte limit
+    const char* v = getenv("SHM_VALTAB");
+    t->vt_on = !(v && v[0] == '0');
+    if (const char* m = getenv("SHM_VALTAB_MAX_BYTES")) t->vt_max_bytes = strtoull(m, nullptr, 0);
   }
   auto fail = [&](int rc) {
     free_all(t);
@@ -1601,6 +1743,7 @@ int shm_search_batch(shm_tree* t, const uint64_t* keys, uint64_t n,
   if (t->reads_since_write < kReadPhase) ++t->reads_since_write;
   if (use_leaf_dir(t)) {
     dir_note_gets(t, n);
+    if (const int rc = vt_poll(t, false)) return rc;
     if (dir_stale(t)) ord.make_exclusive();  // the rebuild rewrites what searches read
     const int rc = ord.rc ? ord.rc : refresh_dir(t, s);
     if (rc) return rc;
@@ -1630,6 +1773,12 @@ static int search_impl(shm_tree* t, hipStream_t s, Order& ord, const uint64_t* k
     set_dir(t, &a.dir, &a.dir_lo, &a.dir_shift, &a.dir_n);
     a.dir_exact = a.dir && t->dir_exact ? 1 : 0;
     a.page_check = (t->cfg.flags & SHM_FLAG_PAGE_CHECK) ? 1 : 0;
+    if (a.dir && !a.page_check && vt_trusted(t)) {
+      a.vt = t->vt;
+      a.vt_lo = t->cfg.key_lo;
+      a.vt_shift = t->cfg.key_bits - t->vt_bits;
+      a.vt_n = 1ull << t->vt_bits;
+    }
     if (use_top(t) && t->top_valid) {
       a.top_keys = t->top_keys;
       a.top_pages = t->top_pages;
@@ -2336,6 +2485,46 @@ int shm__dir_dump(shm_tree* t, void* buf, uint64_t cap_entries, uint64_t* info) 
   if (!buf) return SHM_OK;
   if (cap_entries < n) return SHM_EINVAL;
   HIP_OK(hipMemcpy(buf, t->dir, n * 8 * kDirWords, hipMemcpyDeviceToHost));
+  return SHM_OK;
+}
+
+// test hook: the bucket table (valtab.h): out = {buckets, bytes, dead
+// buckets now, stored keys in dead buckets at the last build, stored keys
+// then, trusted}; all 0 without a table
+int shm__vt_stats(shm_tree* t, uint64_t* out) {
+  if (!t || !out) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  memset(out, 0, 6 * sizeof(uint64_t));
+  if (const int rc = vt_poll(t, true)) return rc;
+  HIP_OK(hipDeviceSynchronize());
+  if (!t->vt || !t->vt_valid) return SHM_OK;
+  out[0] = 1ull << t->vt_bits;
+  out[1] = t->vt_bytes;
+  HIP_OK(hipMemcpy(out + 2, t->vt_ctr, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  out[3] = t->vt_dead_keys;
+  out[4] = t->vt_keys;
+  out[5] = vt_trusted(t) ? 1u : 0u;
+  return SHM_OK;
+}
+
+// test hook: the raw buckets (16 u64 each) for a host-side check
+// (tests/valtab_model.py), in the style of shm__dir_dump; info = {buckets,
+// lo, shift, trusted}, buckets 0 without a table
+int shm__vt_dump(shm_tree* t, void* buf, uint64_t cap_buckets, uint64_t* info) {
+  if (!t || !info) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  memset(info, 0, 4 * sizeof(uint64_t));
+  if (const int rc = vt_poll(t, true)) return rc;
+  HIP_OK(hipDeviceSynchronize());
+  if (!t->vt || !t->vt_valid) return SHM_OK;
+  const uint64_t n = 1ull << t->vt_bits;
+  info[0] = n;
+  info[1] = t->cfg.key_lo;
+  info[2] = t->cfg.key_bits - t->vt_bits;
+  info[3] = vt_trusted(t) ? 1u : 0u;
+  if (!buf) return SHM_OK;
+  if (cap_buckets < n) return SHM_EINVAL;
+  HIP_OK(hipMemcpy(buf, t->vt, n * 8 * dev::kVtBucketWords, hipMemcpyDeviceToHost));
   return SHM_OK;
 }
 
