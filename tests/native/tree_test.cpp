@@ -43,6 +43,21 @@ int main() {
   uint64_t sum = 0;
   for (int i = 0; i < 100; ++i) sum += buf[i];
   CHECK(sum == 3 * (100 + 199) * 100 / 2);
+  // scan(from, limit): the next `limit` keys from `from` on, ascending, with
+  // their values; fewer at the end of the tree; a limit of 0 is refused
+  std::vector<shm::Key> sk(10);
+  std::vector<shm::Value> sv(10);
+  CHECK(tree.scan(100, 10, sk.data(), sv.data()) == 10);
+  for (uint64_t i = 0; i < 10; ++i) CHECK(sk[i] == 100 + i && sv[i] == 3 * (100 + i));
+  CHECK(tree.scan(N - 5, 10, sk.data(), sv.data()) == 5);
+  for (uint64_t i = 0; i < 5; ++i) CHECK(sk[i] == N - 5 + i && sv[i] == 3 * (N - 5 + i));
+  bool refused = false;
+  try {
+    tree.scan(100, 0, sk.data(), sv.data());
+  } catch (const shm::Error& e) {
+    refused = e.status == SHM_EINVAL;
+  }
+  CHECK(refused);
   uint64_t leaves = 0, internal = 0, keys = 0;
   tree.check_tree(&leaves, &internal, &keys);
   CHECK(keys == N - 1);

@@ -23,6 +23,7 @@ torch = pytest.importorskip("torch")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import dir_model  # noqa: E402
+import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
@@ -105,8 +106,7 @@ def next_pow2(x):
     return 1 << max(0, int(x - 1).bit_length())
 
 
-@pytest.mark.parametrize("form", ["fingerprints", "pairs"])
-def test_splitting_chunks_keep_the_directory_current(lib_ok, form):
+def _splitting_chunks(form, table=True):
     """Both directory forms: after the load (fingerprint form) or a read
     phase (pair form), chunks go in with the upkeep on: runs of 30 new keys
     next to stored ones (each splits its leaf), new keys spread over the
@@ -116,9 +116,17 @@ def test_splitting_chunks_keep_the_directory_current(lib_ok, form):
     would call for a denser one), and the share of gets answered from their
     directory entry stays within a few percent of what it was before the
     chunks (the one or two prefixes per split page shared with a neighbour
-    go to the summary walk)."""
+    go to the summary walk).
+
+    The pair form's tree has a key-value bucket table beside the directory
+    (valtab.h), whose answers count as answered from the entry, and the
+    rebuild it is compared with has none: there both shares are taken over
+    the probes the model of the answering path (tests/get_paths.py) does not
+    give to the table -- every stored key outside it, so that the two are
+    measured on the same path -- and table=False runs the whole test on a
+    tree made without one, where that is every probe."""
     n0 = 1 << 18
-    t, orc, base = loaded(n0)
+    t, orc, base = loaded(n0) if table else gp.without_table(lambda: loaded(n0))
     rng = np.random.default_rng(7)
     probe = base[rng.integers(0, n0, 1 << 15)]
     reads = 5 if form == "pairs" else 1  # four searches without an insert: the read phase
@@ -161,6 +169,18 @@ def test_splitting_chunks_keep_the_directory_current(lib_ok, form):
     assert d1["form"] == form
     frac1 = st1["dir_fp_hits"] / max(st1["hits"], 1)
     if form == "pairs":
+        vs = t.vt_stats()
+        assert vs["trusted"] if table else vs["buckets"] == 0, vs
+        cls = gp.classify(probe2, *gp.dumps(t))
+        if table:  # (probe2's own share outside the table is 5 %: too few to resolve 0.002)
+            pool = np.concatenate([stored, probe2[-4096:]])
+            probe2 = pool[gp.classify(pool, *gp.dumps(t)) != gp.TABLE]
+            assert 8192 < probe2.size < pool.size // 4, (probe2.size, pool.size)
+            gv, gf, st1, cls = gp.searched(t, probe2)
+            assert_same(probe2, *orc.search_batch(probe2), gv, gf)
+            frac1 = st1["dir_fp_hits"] / max(st1["hits"], 1)
+        assert not (cls == gp.TABLE).any(), gp.tally(cls)
+        gp.assert_rules(cls, gf, st1, f"kept by the chunks, table {'on' if table else 'off'}")
         # as good as a fresh build: the runs of 30 keys leave ~200 prefixes
         # with more than 16 keys, which no pair entry can list (k_dir_pairs
         # leaves them unusable as well); rebuild (round 5's rules, upkeep
@@ -168,9 +188,13 @@ def test_splitting_chunks_keep_the_directory_current(lib_ok, form):
         t.dir_config(maint=False)
         for _ in range(4):
             gpu_search(t, probe2)
-        gv, gf, st2 = gpu_search(t, probe2, stats=True)
+        gv, gf, st2, cls = gp.searched(t, probe2)
+        assert_same(probe2, *orc.search_batch(probe2), gv, gf)
         assert t.dir_stats()["builds"] > d1["builds"]
+        assert not (cls == gp.TABLE).any(), gp.tally(cls)  # the rebuild has no table
+        gp.assert_rules(cls, gf, st2, "rebuilt")
         frac2 = st2["dir_fp_hits"] / max(st2["hits"], 1)
+        print(f"frac1={frac1:.5f} frac2={frac2:.5f} over {probe2.size} probes")
         assert frac1 >= frac2 - 0.002, (frac1, frac2, st1, st2)
     else:
         assert frac1 >= frac0 - 0.02, (frac0, frac1, st1)  # the repairs after each chunk
@@ -178,6 +202,17 @@ def test_splitting_chunks_keep_the_directory_current(lib_ok, form):
     assert rc == 0 and t.check()["keys"] == oc["keys"]
     orc.close()
     t.close()
+
+
+@pytest.mark.parametrize("form", ["fingerprints", "pairs"])
+def test_splitting_chunks_keep_the_directory_current(lib_ok, form):
+    """both forms on the default tree (the pair form has a bucket table)"""
+    _splitting_chunks(form)
+
+
+def test_splitting_chunks_keep_the_directory_current_without_the_table(lib_ok):
+    """the pair form on a tree made without a bucket table"""
+    _splitting_chunks("pairs", table=False)
 
 
 def test_without_upkeep_the_same_chunks_stay_exact(lib_ok):

@@ -24,7 +24,18 @@ After every chunk (Rig.check): (a) searches of the touched keys, their and
 their neighbouring prefixes' stored and absent keys and a fixed sample equal
 the oracle; (b) the model finds no entry that makes a false claim, and the
 page image equals the oracle's contents; (c) shm__dir_verify is clean; (d) no
-error bit; (e) no rebuild, and the directory is still exact.
+error bit; (e) no rebuild, and the directory is still exact; (f) where the
+tree has a key-value bucket table (valtab.h; every default rig whose keys do
+not crowd into a few buckets), it is still trusted and its raw dump holds
+exactly the oracle's pairs (tests/valtab_model.py): the scenarios put 9, 16
+and 17 new keys of one bucket into one launch, churn, and work at both ends
+of a key range.
+
+The table answers a get before the directory entry is read, so the tests that
+prove "answered by the entry" from the index statistics run twice: on a tree
+without a table (Rig(table=False): SHM_VALTAB=0), where the entry is all a get
+has, and on the default tree, where the model of the answering path
+(tests/get_paths.py) says which probes the table takes.
 """
 import os
 import sys
@@ -40,6 +51,8 @@ torch = pytest.importorskip("torch")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import dir_model as dm  # noqa: E402
+import get_paths as gp  # noqa: E402
+import valtab_model as vm  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
@@ -104,8 +117,12 @@ class Rig:
     """A small tree with the upkeep on for every chunk, its oracle, and the
     model's view of both (refreshed by check())."""
 
-    def __init__(self, form="pairs", keys=None, key_lo=0, key_bits=64, room=None):
-        self.t = shm.Tree(arena_bytes=ARENA, max_batch=MB, key_lo=key_lo, key_bits=key_bits)
+    def __init__(self, form="pairs", keys=None, key_lo=0, key_bits=64, room=None, table=True):
+        def make():  # (SHM_VALTAB is read when the tree is created)
+            return shm.Tree(arena_bytes=ARENA, max_batch=MB, key_lo=key_lo, key_bits=key_bits)
+
+        self.table = table
+        self.t = make() if table else gp.without_table(make)
         self.t.dir_config(maint="always")
         self.orc = OracleTree(ARENA)
         self.rng = np.random.default_rng(31)
@@ -127,6 +144,10 @@ class Rig:
         st = self.t.dir_stats()
         assert st["form"] == form and st["exact"] == 1, st
         self.builds = st["builds"]
+        vs = self.t.vt_stats()
+        self.has_table = bool(vs["trusted"])
+        assert table or vs["buckets"] == 0, vs
+        print(f"rig: form {form}, table {'on' if table else 'off'}: {vs}")
         stored, _ = self.orc.dump()
         self.sample = stored[self.rng.integers(0, stored.size, 512)]
         self.checked = {"pair": 0, "value": 0, "fp": 0}
@@ -213,6 +234,10 @@ class Rig:
         assert st["builds"] == self.builds and st["exact"] == 1, (st, self.builds, t.stats())
         for c in expect:
             assert checked[c] > 0, (c, checked)
+        if self.has_table:  # (f)
+            assert t.vt_stats()["trusted"], t.vt_stats()
+            bad, _ = vm.check_tree(t, okeys, ovals)
+            assert bad == [], bad[:8]
 
     def finish(self):
         rc, oc = self.orc.check()
@@ -332,21 +357,27 @@ def expect_state(rig, tg, flagged, label):
     return int(ok.sum())
 
 
-def reads_no_leaf_entry(rig, keys):
-    """a batch of stored keys answered by value-form entries alone"""
+def reads_no_leaf_entry(rig, keys, label=""):
+    """a batch of stored keys answered by value-form entries alone: without
+    a table the model gives every one of them to the value form; with one,
+    to the value form or to a live bucket"""
     keys = np.asarray(keys, dtype=U64)
-    gv, gf, st = gpu_search(rig.t, keys, stats=True)
+    gv, gf, st, cls = gp.searched(rig.t, keys)
     assert_same(keys, *rig.orc.search_batch(keys), gv, gf)
+    n = gp.assert_rules(cls, gf, st, f"reads no leaf entry {label}")
     assert bool(gf.all()) and st["gets"] == keys.size, st
+    assert n[gp.LEAF] == 0, n
+    if not rig.table:
+        assert n[gp.VALUE] == keys.size, n
     assert st["entry_reads"] == 0 and st["dir_fp_hits"] == st["gets"], st
+    return n
 
 
 def concat(parts):
     return np.concatenate([np.asarray(x, dtype=U64).ravel() for x in parts])
 
 
-@pytest.mark.parametrize("form", ["pairs", "fingerprints"])
-def test_growth_across_the_limits_one_key_per_chunk(lib_ok, form):
+def _growth(form, table):
     """Scenario 1.  Prefixes that start with 0, 1, 2 (built in value form)
     and 3, 4 keys (plain pair form) each get one new key per chunk until
     they hold 17: across 2 -> 3 (the value form ends through the count),
@@ -354,7 +385,9 @@ def test_growth_across_the_limits_one_key_per_chunk(lib_ok, form):
     than pairs: not usable).  The fingerprint form runs the same chunks
     under checks (a)-(e) (its entries carry a byte per slot, no count)."""
     t0 = time.time()
-    rig = Rig(form, room=17)
+    rig = Rig(form, room=17, table=table)
+    assert rig.has_table == (table and form == "pairs"), rig.t.vt_stats()
+    seen = {gp.TABLE: 0, gp.VALUE: 0, gp.LEAF: 0}
     tgs = rig.targets([0, 1, 2, 3, 4], add=17)
     for c, tg in tgs.items():
         assert tg.p.size >= MIN_TARGETS, (c, tg.p.size)
@@ -384,7 +417,12 @@ def test_growth_across_the_limits_one_key_per_chunk(lib_ok, form):
                 continue
             done[c] = expect_state(rig, tg, flagged=c <= 2, label=(c, step))
             if c <= 2 and now <= 2 and ok.any():
-                reads_no_leaf_entry(rig, concat([x for x, o in zip(tg.keys(), ok) if o]))
+                n = reads_no_leaf_entry(rig, concat([x for x, o in zip(tg.keys(), ok) if o]),
+                                        f"(scenario 1, class {c}, step {step})")
+                seen = {x: seen[x] + n[x] for x in seen}
+    if form == "pairs":  # with the table on nearly every such get is the table's
+        print(f"scenario 1: keys of small prefixes per class {seen}")
+        assert seen[gp.VALUE] > 0 if not table else seen[gp.TABLE] > 0.9 * sum(seen.values()), seen
     print(f"scenario 1 [{form}]: unsplit targets per class {done}, model checked {rig.checked}, "
           f"{time.time() - t0:.2f} s")
     for c, n in done.items():
@@ -392,13 +430,24 @@ def test_growth_across_the_limits_one_key_per_chunk(lib_ok, form):
     rig.finish()
 
 
-@pytest.mark.parametrize("k", [2, 3, 8, 9, 16, 17])
-def test_the_same_limits_inside_one_launch(lib_ok, k):
+@pytest.mark.parametrize("form", ["pairs", "fingerprints"])
+def test_growth_across_the_limits_one_key_per_chunk(lib_ok, form):
+    """scenario 1 on the default tree (a bucket table beside the pair form)"""
+    _growth(form, True)
+
+
+def test_growth_across_the_limits_one_key_per_chunk_without_the_table(lib_ok):
+    """scenario 1 on a tree made without a bucket table: the value form answers"""
+    _growth("pairs", False)
+
+
+def _same_limits(k, table):
     """Scenario 2.  One chunk adds k keys to each target that held 0 keys or
     1 key: the lanes of one launch race for the pair positions and the
     inline entries; the states are scenario 1's for the resulting count."""
     t0 = time.time()
-    rig = Rig(room=k)
+    rig = Rig(room=k, table=table)
+    assert rig.has_table == table, rig.t.vt_stats()
     tgs = rig.targets([0, 1], add=k)
     new = concat([tg.fresh(k) for tg in tgs.values()])
     rig.rng.shuffle(new)
@@ -410,7 +459,8 @@ def test_the_same_limits_inside_one_launch(lib_ok, k):
         assert np.all(tg.counts()[ok] == c + k), (c, k)
         done[c] = expect_state(rig, tg, flagged=True, label=(c, k))
         if c + k <= 2 and ok.any():
-            reads_no_leaf_entry(rig, concat([x for x, o in zip(tg.keys(), ok) if o]))
+            reads_no_leaf_entry(rig, concat([x for x, o in zip(tg.keys(), ok) if o]),
+                                f"(scenario 2, k={k}, class {c})")
     print(f"scenario 2 [k={k}]: unsplit targets per class {done}, model checked {rig.checked}, "
           f"{time.time() - t0:.2f} s")
     for c, n in done.items():
@@ -418,7 +468,19 @@ def test_the_same_limits_inside_one_launch(lib_ok, k):
     rig.finish()
 
 
-def test_one_chunk_mixes_ops_on_a_value_form_prefix(lib_ok):
+@pytest.mark.parametrize("k", [2, 3, 8, 9, 16, 17])
+def test_the_same_limits_inside_one_launch(lib_ok, k):
+    """scenario 2 on the default tree (with the bucket table)"""
+    _same_limits(k, True)
+
+
+@pytest.mark.parametrize("k", [2, 3, 8, 9, 16, 17])
+def test_the_same_limits_inside_one_launch_without_the_table(lib_ok, k):
+    """scenario 2 on a tree made without a bucket table"""
+    _same_limits(k, False)
+
+
+def _one_chunk_mixes_ops(table):
     """Scenario 3.  Prefixes {A, B} held inline; one chunk, a case per set
     of targets: delete A + new C; update A + new C; delete A and B + two new
     keys; A deleted and re-inserted; A updated twice (the last writer wins).
@@ -428,7 +490,8 @@ def test_one_chunk_mixes_ops_on_a_value_form_prefix(lib_ok):
     count its pair before A's lane looks: the entry then holds three or four
     pairs, A's dead one among them, and is served as a plain pair entry.)"""
     t0 = time.time()
-    rig = Rig(room=2)
+    rig = Rig(room=2, table=table)
+    assert rig.has_table == table, rig.t.vt_stats()
     all2 = rig.targets([2], add=2, per_class=5 * MIN_TARGETS + 40)[2]
     assert all2.p.size >= 5 * MIN_TARGETS, all2.p.size
     n = all2.p.size // 5
@@ -470,7 +533,8 @@ def test_one_chunk_mixes_ops_on_a_value_form_prefix(lib_ok):
         inline = name in ("del+reins", "upd2")
         done[name] = expect_state(rig, tg, flagged=inline, label=name)
         if inline:
-            reads_no_leaf_entry(rig, concat([x for x, o in zip(tg.keys(), ok) if o]))
+            reads_no_leaf_entry(rig, concat([x for x, o in zip(tg.keys(), ok) if o]),
+                                f"(scenario 3, {name})")
     print(f"scenario 3: unsplit targets per case {done}, model checked {rig.checked}, "
           f"{time.time() - t0:.2f} s")
     for name, m in done.items():
@@ -478,7 +542,17 @@ def test_one_chunk_mixes_ops_on_a_value_form_prefix(lib_ok):
     rig.finish()
 
 
-def test_churn_keeps_small_prefixes_usable(lib_ok):
+def test_one_chunk_mixes_ops_on_a_value_form_prefix(lib_ok):
+    """scenario 3 on the default tree (with the bucket table)"""
+    _one_chunk_mixes_ops(True)
+
+
+def test_one_chunk_mixes_ops_on_a_value_form_prefix_without_the_table(lib_ok):
+    """scenario 3 on a tree made without a bucket table"""
+    _one_chunk_mixes_ops(False)
+
+
+def _churn(table):
     """Scenario 4.  Sixteen rounds: a chunk deletes one key
     of every target, the next re-inserts it with a new value.  The pair of a
     deleted key is never removed, so a prefix of 3 keys reaches 16 pairs
@@ -488,7 +562,8 @@ def test_churn_keeps_small_prefixes_usable(lib_ok):
     answered through its entry.  (Before: the entry was marked bad for
     good, correct results through the summary walk.)"""
     t0 = time.time()
-    rig = Rig(room=1)
+    rig = Rig(room=1, table=table)
+    assert rig.has_table == table, rig.t.vt_stats()
     tgs = rig.targets([1, 3], add=1)
     for c, tg in tgs.items():
         assert tg.p.size >= MIN_TARGETS, (c, tg.p.size)
@@ -505,14 +580,34 @@ def test_churn_keeps_small_prefixes_usable(lib_ok):
         assert np.all(tg.counts()[ok] == c), c
         done[c] = expect_state(rig, tg, flagged=c <= 2, label=("churn", c))
         keys = concat([x for x, o in zip(tg.keys(), ok) if o])
-        gv, gf, st = gpu_search(rig.t, keys, stats=True)
-        assert_same(keys, *rig.orc.search_batch(keys), gv, gf)
+        # a prefix of 3 keys is answered through its pairs, reading a leaf
+        # entry per key, unless a live bucket holds it: the keys the model
+        # does not give to the table are held to that on their own
+        _, gf, st, cls = gp.check_paths(rig.t, rig.orc, keys, table, f"scenario 4, class {c}")
         assert bool(gf.all()) and st["dir_fp_hits"] == st["gets"] == keys.size, (c, st)
+        want = gp.VALUE if c <= 2 else gp.LEAF
+        assert np.all(cls[cls != gp.TABLE] == want), (c, gp.tally(cls))
+        rest = keys[cls != gp.TABLE]
+        if rest.size:
+            gv, gf, st, _ = gp.searched(rig.t, rest)
+            assert_same(rest, *rig.orc.search_batch(rest), gv, gf)
+            assert bool(gf.all()) and st["dir_fp_hits"] == st["gets"] == rest.size, (c, st)
+        assert table or rest.size == keys.size
     print(f"scenario 4: unsplit targets per class {done}, model checked {rig.checked}, "
           f"{time.time() - t0:.2f} s")
     for c, m in done.items():
         assert m >= MIN_TARGETS, (c, m)
     rig.finish()
+
+
+def test_churn_keeps_small_prefixes_usable(lib_ok):
+    """scenario 4 on the default tree (with the bucket table)"""
+    _churn(True)
+
+
+def test_churn_keeps_small_prefixes_usable_without_the_table(lib_ok):
+    """scenario 4 on a tree made without a bucket table"""
+    _churn(False)
 
 
 def raw_fp_byte(k):

@@ -23,6 +23,7 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import dir_model  # noqa: E402
+import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
@@ -96,6 +97,17 @@ def loaded(maint="always", max_batch=1 << 18, **kw):
     return t, orc, base
 
 
+def loaded_table(table, **kw):
+    """loaded() with the key-value bucket table ("on": the default) or
+    without one ("off": SHM_VALTAB=0 while the tree is created).  Off, the
+    directory's entries are all a get has; on, they serve only the keys of
+    dead buckets, and the tests ask the model (tests/get_paths.py) which."""
+    t, orc, base = loaded(**kw) if table == "on" else gp.without_table(lambda: loaded(**kw))
+    vs = t.vt_stats()
+    assert vs["trusted"] if table == "on" else vs["buckets"] == 0, (table, vs)
+    return t, orc, base
+
+
 class Prefixes:
     """The directory's prefixes of a key set, on the host: key >> shift for a
     directory of `entries` prefixes over the 64-bit key space."""
@@ -140,24 +152,37 @@ def verify_clean(t):
     return v
 
 
-def test_small_prefixes_are_answered_by_the_entry_alone(lib_ok):
+def _small_prefixes(table):
     """Stored probes whose prefix holds at most two keys read no leaf entry:
     with q their share, a batch reads at most 1.05 (1 - q) entries per get
     (the 5 %: fingerprint false candidates), every get is still answered
     from its directory entry, absent keys are absent, and the verify finds
-    value-form entries, none wrong."""
-    t, orc, base = loaded()
+    value-form entries, none wrong.  Without the bucket table that is the
+    whole batch; with it, the batch of the probes the model does not give to
+    the table (a live bucket answers before the entry is read, and counts as
+    a get answered from its entry with no entry read).  Both: at least one
+    entry read per stored probe the model sends to the leaves, none in a
+    batch it sends nowhere near them."""
+    t, orc, base = loaded_table(table)
     px = Prefixes(t, base)
     rng = np.random.default_rng(21)
     probe = base[rng.integers(0, N0, 1 << 15)]
     q = float(np.mean(px.held(probe) <= 2))
     assert 0.3 < q < 0.5, q  # 1 + Poisson(2) keys in a key's prefix: 40.6 %
-    gv, gf, st = gpu_search(t, probe, stats=True)
-    assert_same(probe, *orc.search_batch(probe), gv, gf)
-    print(f"q={q:.4f} gets={st['gets']} entry_reads={st['entry_reads']} "
-          f"dir_fp_hits={st['dir_fp_hits']} bound={1.05 * (1 - q) * st['gets']:.0f}")
+
+    def upper(st, keys, found):
+        qk = float(np.mean(px.held(keys) <= 2))
+        print(f"q={qk:.4f} gets={st['gets']} entry_reads={st['entry_reads']} "
+              f"dir_fp_hits={st['dir_fp_hits']} bound={1.05 * (1 - qk) * st['gets']:.0f}")
+        assert bool(found.all()) and st["dir_fp_hits"] == st["gets"], st
+        assert st["entry_reads"] <= 1.05 * (1 - qk) * st["gets"], (qk, st)
+
+    _, _, st, cls = gp.check_paths(t, orc, probe, table == "on", f"small prefixes, table {table}", upper)
     assert st["dir_fp_hits"] == st["gets"], st
-    assert st["entry_reads"] <= 1.05 * (1 - q) * st["gets"], (q, st)
+    if table == "on":  # uniform keys, four per bucket: 94.8 % in live buckets
+        assert np.mean(cls == gp.TABLE) > 0.9, gp.tally(cls)
+    else:  # the value form's share is q: a prefix of at most two keys is held inline
+        assert np.array_equal(cls == gp.VALUE, px.held(probe) <= 2), gp.tally(cls)
     absent = gen_keys(t, N0 + 1, 1 << 13)
     gv, gf, _ = gpu_search(t, absent)
     assert_same(absent, *orc.search_batch(absent), gv, gf)
@@ -167,14 +192,26 @@ def test_small_prefixes_are_answered_by_the_entry_alone(lib_ok):
     t.close()
 
 
-def test_chunks_keep_the_inline_copies_equal_to_the_tree(lib_ok):
+def test_small_prefixes_are_answered_by_the_entry_alone(lib_ok):
+    """with the bucket table (the default tree)"""
+    _small_prefixes("on")
+
+
+def test_small_prefixes_are_answered_by_the_entry_alone_without_the_table(lib_ok):
+    """on a tree made without a bucket table: every probe goes through its entry"""
+    _small_prefixes("off")
+
+
+def _chunks_keep_the_copies(table):
     """Upkeep on for every chunk: in-place updates and deletes of keys held
     inline, new keys into prefixes of 0, 1 and 2 keys, and runs of 30 keys
     that split leaves, one chunk each.  After each: the touched keys and
     their prefixes' neighbours equal the oracle, the verify is clean, the
     directory was not rebuilt, and gets are still answered by value-form
-    entries (fewer entry reads than hits)."""
-    t, orc, base = loaded()
+    entries (fewer entry reads than hits: over the whole batch without the
+    bucket table, over the probes the model does not give to the table with
+    it), under the model's rules for each path (get_paths.check_paths)."""
+    t, orc, base = loaded_table(table)
     px = Prefixes(t, base)
     rng = np.random.default_rng(22)
     builds = t.dir_stats()["builds"]
@@ -206,13 +243,25 @@ def test_chunks_keep_the_inline_copies_equal_to_the_tree(lib_ok):
         # in prefixes of ~30 keys, which no pair-form entry lists)
         touched = np.unique(np.concatenate([touched, sample]))
         touched = touched[(touched != U64(shm.KEY_MAX)) & (touched != U64(0))]
-        gv, gf, st = gpu_search(t, touched, stats=True)
-        assert_same(touched, *orc.search_batch(touched), gv, gf)
+        def upper(st, keys, found, name=name):  # value-form answers still occur
+            assert st["entry_reads"] < st["hits"], (name, st)
+
+        on, held_to_bound = table == "on", touched
+        if on and name == "split":
+            # The run keys sit in prefixes of ~30 keys, which no pair-form
+            # entry lists: each is a summary walk with false candidates.
+            # Without the table the sample's value-form hits (40 % of it)
+            # outweigh those; with it the sample's share outside the table
+            # is 5 %, so the bound is held on the other probes, and the runs
+            # on the rules alone.
+            gp.check_paths(t, orc, touched, True, f"{name}, table on, with the runs")
+            held_to_bound = touched[~np.isin(touched, runs)]
+        _, _, st, _ = gp.check_paths(t, orc, held_to_bound, on, f"{name}, table {table}", upper)
         v1 = verify_clean(t)
         print(name, st, v1)
         assert v1["vals_checked"] > 0, (name, v1)
         assert t.dir_stats()["builds"] == builds, (name, t.dir_stats())
-        assert st["entry_reads"] < st["hits"], (name, st)  # value-form answers still occur
+        assert t.vt_stats()["trusted"] == (table == "on"), (name, t.vt_stats())
     assert t.last_error()["bits"] == 0
     rc, oc = orc.check()
     assert rc == 0 and t.check()["keys"] == oc["keys"]
@@ -220,13 +269,24 @@ def test_chunks_keep_the_inline_copies_equal_to_the_tree(lib_ok):
     t.close()
 
 
-@pytest.mark.parametrize("how", ["off", "unsearched"])
-def test_chunks_without_upkeep_end_the_trust(lib_ok, how):
+def test_chunks_keep_the_inline_copies_equal_to_the_tree(lib_ok):
+    """with the bucket table (the default tree)"""
+    _chunks_keep_the_copies("on")
+
+
+def test_chunks_keep_the_inline_copies_equal_to_the_tree_without_the_table(lib_ok):
+    """on a tree made without a bucket table"""
+    _chunks_keep_the_copies("off")
+
+
+def _chunks_without_upkeep(how, table):
     """Chunks that do not keep the directory -- the upkeep switched off after
     the build, or the default policy's chunk with no search before it --
-    leave stale inline copies behind; the directory is then not exact and
-    the gets ignore the form: updated and deleted keys equal the oracle."""
-    t, orc, base = loaded(maint="always" if how == "off" else True)
+    leave stale inline copies (and, with a bucket table, stale buckets)
+    behind; the directory is then not exact and the gets ignore both:
+    updated and deleted keys equal the oracle, the model sends every probe
+    to the leaves, and every stored one does read a leaf entry."""
+    t, orc, base = loaded_table(table, maint="always" if how == "off" else True)
     px = Prefixes(t, base)
     rng = np.random.default_rng(23)
     assert t.dir_verify()["vals_checked"] > 0
@@ -243,12 +303,26 @@ def test_chunks_without_upkeep_end_the_trust(lib_ok, how):
     v = np.concatenate([upd ^ U64(0xABCDEF), np.zeros(dele.size, dtype=U64)])
     t.insert_batch(dev(k), dev(v))
     orc.apply_batch(k, v)
-    assert not t.dir_stats()["exact"]
+    assert not t.dir_stats()["exact"] and not t.vt_stats()["trusted"]
     probe = np.concatenate([k, small[pick[8000:12000]]])
-    gv, gf, _ = gpu_search(t, probe)
-    assert_same(probe, *orc.search_batch(probe), gv, gf)
+    _, gf, st, cls = gp.check_paths(t, orc, probe, False, f"unkept chunk ({how}), table {table}")
+    assert (cls == gp.LEAF).all(), gp.tally(cls)
+    assert st["entry_reads"] >= int(gf.sum()) == st["hits"] > 0, st
+    assert not t.vt_stats()["trusted"]
     orc.close()
     t.close()
+
+
+@pytest.mark.parametrize("how", ["off", "unsearched"])
+def test_chunks_without_upkeep_end_the_trust(lib_ok, how):
+    """with the bucket table: its trust ends with the directory's"""
+    _chunks_without_upkeep(how, "on")
+
+
+@pytest.mark.parametrize("how", ["off", "unsearched"])
+def test_chunks_without_upkeep_end_the_trust_without_the_table(lib_ok, how):
+    """on a tree made without a bucket table"""
+    _chunks_without_upkeep(how, "off")
 
 
 def _stored_batch_reads_every_hit(t, orc, base):

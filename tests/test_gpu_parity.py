@@ -9,6 +9,8 @@ B-link invariants; and each side's page image is searchable by the other
 All GPU work runs in this one process.
 """
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -17,6 +19,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree, op_mix, to_key, zipf_fill  # noqa: E402
 
@@ -1435,7 +1440,7 @@ def test_early_split_block_list_overflow(lib_ok):
     t.close()
 
 
-def test_directory_ties_start_at_the_leaf(lib_ok):
+def _directory_ties(table):
     """A directory entry's split points are the top 32 bits of each leaf's
     lowest fence within the prefix, so a lookup of a leaf's FIRST key ties
     with its split point (round 4: 2.7 % of C2's gets did, and started one
@@ -1443,8 +1448,18 @@ def test_directory_ties_start_at_the_leaf(lib_ok):
     the safe start only when the key is not there: with a fresh directory,
     gets and in-place updates of every leaf's first key make no right move,
     and keys just below / above those fences (absent) still come back
-    exactly as the oracle says."""
-    t = shm.Tree(arena_bytes=512 << 20, max_batch=1 << 18)
+    exactly as the oracle says.
+
+    A live bucket of the key-value table (valtab.h) answers a get before any
+    directory entry is read, so with a table only the first keys in dead
+    buckets ever start a tie: the model of the answering path
+    (tests/get_paths.py) picks them out, and table=False runs the test on a
+    tree made without a table, where every first key goes through its
+    entry."""
+    def make():
+        return shm.Tree(arena_bytes=512 << 20, max_batch=1 << 18)
+
+    t = make() if table else gp.without_table(make)
     orc = OracleTree(512 << 20)
     ks = hashed_keys(1, 300001)
     for c in range(0, ks.size, 1 << 17):
@@ -1459,14 +1474,18 @@ def test_directory_ties_start_at_the_leaf(lib_ok):
     assert seps.size > 1000
     for _ in range(6):  # a read phase: the directory is rebuilt exact
         gpu_search(t, ks[:4096])
-    t.profile(False, index_stats=True)
-    gv, gf = gpu_search(t, seps)
-    st = t.index_stats()
+    vs = t.vt_stats()
+    assert vs["trusted"] if table else vs["buckets"] == 0, vs
+
+    def no_right_move(st, keys, found):
+        assert bool(found.all()) and st["right_moves"] == 0, st
+
+    _, _, st, cls = gp.check_paths(t, orc, seps, table, f"first keys, table {'on' if table else 'off'}",
+                                   no_right_move)
     assert st["right_moves"] == 0, st
-    assert_same(seps, *orc.search_batch(seps), gv, gf)
+    assert int((cls != gp.TABLE).sum()) > (0 if table else 1000), gp.tally(cls)
     near = np.concatenate([seps - U64(1), seps + U64(1)])
     gv, gf = gpu_search(t, near)
-    t.profile(False)
     assert_same(near, *orc.search_batch(near), gv, gf)
     # in-place updates of the first keys, then new keys right below them
     # (they belong to the leaf on the left): contents equal the oracle
@@ -1480,6 +1499,16 @@ def test_directory_ties_start_at_the_leaf(lib_ok):
     compare_contents(t, orc)
     orc.close()
     t.close()
+
+
+def test_directory_ties_start_at_the_leaf(lib_ok):
+    """on the default tree: the ties are the first keys in dead buckets"""
+    _directory_ties(True)
+
+
+def test_directory_ties_start_at_the_leaf_without_the_table(lib_ok):
+    """on a tree made without a bucket table: every first key ties"""
+    _directory_ties(False)
 
 
 @pytest.mark.parametrize("start", ["dir", "lds", "root"])
@@ -1575,7 +1604,7 @@ def test_pending_range_waits_for_its_issue_stream(lib_ok):
     t.close()
 
 
-def test_pair_form_directory_reads_through_stale_pairs(lib_ok):
+def _stale_pairs(table):
     """A read phase builds the pair-form directory (layout.h kDirPairs: each
     prefix lists its own keys' slots): every get of the current tree is then
     answered from its entry.  Inserts that split leaves, in-place updates and
@@ -1583,9 +1612,18 @@ def test_pair_form_directory_reads_through_stale_pairs(lib_ok):
     next searches read stale pairs -- moved keys, emptied and overwritten
     slots, keys the pairs never listed -- and must still equal the oracle
     (a pair is only a slot to read; a miss takes the summary walk).  The
-    next read phase rebuilds the pairs, and the contents stay exact."""
+    next read phase rebuilds the pairs, and the contents stay exact.
+
+    "From its entry" also counts the answers of the key-value bucket table
+    (valtab.h), which reads no entry: with a table the statement is held on
+    the probes the model (tests/get_paths.py) does not give to it, and
+    table=False runs the test on a tree made without one."""
     n0 = 1 << 18
-    t = shm.Tree(arena_bytes=512 << 20, max_batch=1 << 18)
+
+    def make():
+        return shm.Tree(arena_bytes=512 << 20, max_batch=1 << 18)
+
+    t = make() if table else gp.without_table(make)
     orc = OracleTree(512 << 20)
     base = hashed_keys(1, n0 + 1)
     bv = np.arange(1, n0 + 1, dtype=U64) * U64(2)
@@ -1596,12 +1634,16 @@ def test_pair_form_directory_reads_through_stale_pairs(lib_ok):
     for _ in range(5):  # four searches without an insert: the read phase
         gv, gf = gpu_search(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
-    t.profile(False, index_stats=True)
-    gv, gf = gpu_search(t, probe)
-    st = t.index_stats()
-    t.profile(False)
-    assert_same(probe, *orc.search_batch(probe), gv, gf)
+    vs = t.vt_stats()
+    assert vs["trusted"] if table else vs["buckets"] == 0, vs
+
+    def all_from_the_entries(st, keys, found):
+        assert bool(found.all()) and st["dir_fp_hits"] == st["gets"] == keys.size, st
+
+    _, _, st, cls = gp.check_paths(t, orc, probe, table, f"read phase, table {'on' if table else 'off'}",
+                                   all_from_the_entries)
     assert st["dir_fp_hits"] == st["gets"] == probe.size, st  # all from the entries
+    assert int((cls != gp.TABLE).sum()) > (0 if table else probe.size - 1), gp.tally(cls)
     # updates, deletes and splitting inserts, no rebuild in between
     upd = base[rng.integers(0, n0, 5000)]
     dele = base[rng.integers(0, n0, 3000)]
@@ -1624,3 +1666,13 @@ def test_pair_form_directory_reads_through_stale_pairs(lib_ok):
     assert rc == 0 and t.check()["keys"] == oc["keys"]
     orc.close()
     t.close()
+
+
+def test_pair_form_directory_reads_through_stale_pairs(lib_ok):
+    """on the default tree (with the bucket table)"""
+    _stale_pairs(True)
+
+
+def test_pair_form_directory_reads_through_stale_pairs_without_the_table(lib_ok):
+    """on a tree made without a bucket table"""
+    _stale_pairs(False)

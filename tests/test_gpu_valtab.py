@@ -21,6 +21,7 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import valtab_model as vm  # noqa: E402
+from get_paths import with_env, without_table  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
@@ -92,18 +93,6 @@ def loaded(maint="always", max_batch=1 << 18, keys=None, mem_limit=0, **kw):
     d = t.dir_stats()
     assert d["form"] == "pairs", d
     return t, orc, base
-
-
-def with_env(name, value, fn):
-    old = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            del os.environ[name]
-        else:
-            os.environ[name] = old
 
 
 class Buckets:
@@ -317,7 +306,7 @@ def test_switches_read_every_hit_from_its_leaf(lib_ok, switch):
     if switch == "page_check":
         t, orc, base = loaded(page_check=True)
     else:
-        t, orc, base = with_env(switch, "0", loaded)
+        t, orc, base = without_table(loaded) if switch == "SHM_VALTAB" else with_env(switch, "0", loaded)
     vs = t.vt_stats()
     assert vs["buckets"] == 0 or switch == "page_check", vs
     ent = t.dir_stats()["entries"]
