@@ -637,6 +637,13 @@ class Tree:
         m = -1 if maint is None else 2 if maint == "always" else int(bool(maint))
         _check(_hooks().shm__dir_config(self.h, m, mem_limit), "dir_config")
 
+    def get_forms(self, coop=None, pack=None):
+        """Test hook (shm__get_forms): the batched get's forms behind a
+        bucket table for this tree's later launches, as SHM_GET_COOP and
+        SHM_GET_PACK set them when the tree is created (None: as is)."""
+        _check(_hooks().shm__get_forms(self.h, -1 if coop is None else int(bool(coop)),
+                                       -1 if pack is None else int(bool(pack))), "get_forms")
+
     def dir_verify(self):
         """Diagnostics (shm__dir_verify): every directory entry the walks
         trust checked against the tree as it is now."""
@@ -762,6 +769,7 @@ _HOOKS = [
     ("shm__dir_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
     ("shm__vt_stats", ctypes.c_int, [vp, ctypes.POINTER(u64)]),
     ("shm__vt_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
+    ("shm__get_forms", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
 ]
 
 

@@ -335,15 +335,25 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
 // 19572 / 19611 and 14828 / 14986 at 5.  With the bucket table's probe in
 // front (valtab.h: 32 more registers live until the probe ends) still 95
 // VGPRs, no scratch, 5 waves (PCHK, which has no probe: 96).
+// COOP / PACK (WalkArgs get_coop / get_pack, chosen per launch, only with a
+// table): the probe that loads each bucket line with one instruction, and
+// the packing of the gets the table leaves over into the block's lowest
+// waves.  Either or both: 95-96 VGPRs, no scratch, 5
+// waves; PACK adds TPB x 12 + TPB / 16 B of static LDS (3088 B at 256).  The
+// packed get's output index is kept as its 32-bit thread number: as a
+// 64-bit index the COOP + PACK form spilled one register.
 // PCHK (SHM_FLAG_PAGE_CHECK): the page-level version check on the fast
 // path too -- a hit read from a page's entry also reads that page's
 // front_version (byte 8) and rear_version (byte 1016) and reports a
 // mismatch (kErrInconsistent: check_consistent, Tree.h:241-261, Tree.cpp:
 // 616-618); two more lines per get (DESIGN §3.5 measures it)
-template <int TPB, bool PCHK>
+template <int TPB, bool PCHK, bool COOP, bool PACK>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k_get_sum(WalkArgs a) {
+  static_assert(!PCHK || (!COOP && !PACK), "the page check has no probe");
   extern __shared__ __attribute__((aligned(16))) uint8_t s_top[];  // top_n x (8 + 4) B
-  const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  // the get's thread of the block: its key and its result are at block base + ti
+  const uint64_t bbase = (uint64_t)blockIdx.x * TPB;
+  uint32_t ti = threadIdx.x;
   const uint32_t tn = a.top_n;
   uint64_t* tk = reinterpret_cast<uint64_t*>(s_top);
   uint32_t* tpg = reinterpret_cast<uint32_t*>(s_top + 8 * (uint64_t)tn);
@@ -355,33 +365,129 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k
     __syncthreads();
   }
   if (a.clk && threadIdx.x == 0) a.clk[blockIdx.x] = wall_clock64();
-  const bool act = i < a.n;
-  const uint64_t k = act ? a.keys[i] : kKeyMax;
+  bool act = bbase + ti < a.n;
+  uint64_t k = act ? a.keys[bbase + ti] : kKeyMax;
   uint64_t val = 0;
   uint32_t err = 0;
   uint32_t c_int = 0, c_right = 0, c_hops = 0, c_ent = 0;
   bool hit = false;
   uint32_t pv_f = 0, pv_r = 0;  // PCHK: the hit page's front / rear versions
+  bool done = false;            // val is the answer
+  // a get is counted where it enters the kernel (the packing below hands it
+  // to another lane)
+  uint32_t c_gets = act && k != kKeyMax ? 1u : 0u;
+  auto add_stats = [&]() {  // wave-uniform; every lane of the wave is here
+    const uint32_t v[kIdxStats] = {wave_sum32(c_gets), wave_sum32(c_int),
+                                   wave_sum32(c_right), wave_sum32(c_hops), wave_sum32(c_ent),
+                                   wave_sum32(act && val != kValueNull ? 1u : 0u),
+                                   wave_sum32(hit ? 1u : 0u)};
+    if (lane_id() == 0)
+      for (int j = 0; j < kIdxStats; ++j)
+        if (v[j]) atomicAdd(reinterpret_cast<unsigned long long*>(a.stats + j), v[j]);
+  };
+  // the bucket table (valtab.h) first: one 128 B line holds every key of
+  // k's bucket, so a live bucket answers the get -- the key's value, or
+  // absent -- with this one request; a dead bucket (more than 8 keys) goes
+  // on below as before.  The 32 bucket registers are dead past this block.
+  if (!PCHK && a.vt) {  // uniform over the launch
+    uint64_t b;
+    const bool hb = vt_bucket_of(a.vt_lo, a.vt_shift, a.vt_n, k, &b);  // never kKeyMax
+    if (COOP) {
+      // One load instruction per bucket line: in round r the eight lanes of
+      // group g = lane >> 3 load the eight slots of the bucket of the get
+      // that lane 8 r + g owns, so a wave instruction reads eight whole
+      // lines and no later one touches them (a lane loading its own bucket
+      // touches 64 lines per instruction, each of them eight times).  All
+      // eight rounds are issued before the first compare.
+      const int lane = lane_id(), g = lane >> 3, sl = lane & 7;
+      u32x4 w[kVtSlots];
+      uint64_t ok[kVtSlots];  // the owners' keys
+#pragma unroll
+      for (int r = 0; r < kVtSlots; ++r) {
+        ok[r] = shfl64(k, 8 * r + g);
+        uint64_t ob;
+        w[r] = u32x4{0u, 0u, 0u, 0u};  // no bucket, no load: a free slot
+        if (vt_bucket_of(a.vt_lo, a.vt_shift, a.vt_n, ok[r], &ob))
+          w[r] = reinterpret_cast<const u32x4*>(a.vt + kVtBucketWords * ob)[sl];
+      }
+#pragma unroll
+      for (int r = 0; r < kVtSlots; ++r) {
+        uint64_t sv;
+        const uint64_t M = ballot(vt_slot_match(w[r], ok[r], &sv));
+        const uint64_t D = ballot(sl == 0 && vt_slot_dead(w[r]));
+        // the owner of round r, lane 8 r + sl, was served by group sl:
+        // vt_probe's answer from that group's eight predicates
+        const uint32_t mg = (uint32_t)(M >> (8 * sl)) & 0xFFu;
+        const bool dg = ((D >> (8 * sl)) & 1ull) != 0;
+        const uint64_t v = shfl64(sv, 8 * sl + (mg ? 31 - __builtin_clz(mg) : 0));
+        if (g == r && hb && !dg) {
+          done = true;
+          if (mg) {
+            val = v;
+            hit = true;
+          }
+        }
+      }
+    } else if (hb) {
+      const u32x4* bp = reinterpret_cast<const u32x4*>(a.vt + kVtBucketWords * b);
+      u32x4 w[kVtSlots];
+#pragma unroll
+      for (int j = 0; j < kVtSlots; ++j) w[j] = bp[j];
+      const int r = vt_probe(w, k, &val);
+      hit = r >= 0;
+      done = r != kVtDead;
+    }
+    if (PACK) {
+      // The gets the table did not answer (a dead bucket, key 0, a key
+      // outside the table's range) are few per wave, and each would keep its
+      // wave resident through the directory path's dependent rounds.  The
+      // answered lanes store now; the block's other gets are packed, in
+      // thread order, into its lowest waves, which alone go on.
+      __shared__ uint64_t s_pk[TPB];           // the packed gets' keys
+      __shared__ uint32_t s_pt[TPB];           // ... and the threads they came from
+      __shared__ uint32_t s_pc[TPB / kWave];   // per wave
+      const int lane = lane_id(), wv = (int)(threadIdx.x / kWave);
+      const bool fall = c_gets && !done;
+      if (act && !fall) {
+        a.out_val[bbase + ti] = val;
+        if (a.out_found) a.out_found[bbase + ti] = val != kValueNull ? 1 : 0;
+      }
+      if (a.stats) add_stats();
+      // a wave's gets go to its own 64 slots, so one barrier is enough: the
+      // readers find slot p of the packed order from the waves' counts
+      const uint64_t fm = ballot(fall);
+      if (fall) {
+        const int at = wv * kWave + popc64(fm & lanemask_lt());
+        s_pk[at] = k;
+        s_pt[at] = threadIdx.x;
+      }
+      if (lane == 0) s_pc[wv] = (uint32_t)popc64(fm);
+      __syncthreads();
+      const uint32_t p = threadIdx.x;
+      uint32_t base = 0;
+      int src = -1;
+#pragma unroll
+      for (int j = 0; j < TPB / kWave; ++j) {
+        const uint32_t c = s_pc[j];
+        if (p >= base && p - base < c) src = j * kWave + (int)(p - base);
+        base += c;
+      }
+      if ((uint32_t)(wv * kWave) >= base) {  // wave-uniform: nothing left for this wave
+        if (a.clk && lane == 0)
+          a.clk[gridDim.x + blockIdx.x * (TPB / kWave) + wv] = wall_clock64();
+        return;
+      }
+      act = src >= 0;
+      k = act ? s_pk[src] : kKeyMax;
+      ti = act ? s_pt[src] : 0u;
+      val = 0;
+      hit = done = false;
+      c_gets = 0;
+    }
+  }
   if (k != kKeyMax) {  // never stored (root highest is exclusive, Tree.h:150)
     uint64_t ptr = a.root;
     uint64_t alt = 0;  // a tie's safe start (dir_start_e)
-    bool done = false;  // val is the answer
-    // the bucket table (valtab.h) first: one 128 B line holds every key of
-    // k's bucket, so a live bucket answers the get -- the key's value, or
-    // absent -- with this one request; a dead bucket (more than 8 keys) goes
-    // on below as before.  The 32 bucket registers are dead past this block.
-    if (!PCHK && a.vt) {
-      uint64_t b;
-      if (vt_bucket_of(a.vt_lo, a.vt_shift, a.vt_n, k, &b)) {
-        const u32x4* bp = reinterpret_cast<const u32x4*>(a.vt + kVtBucketWords * b);
-        u32x4 w[kVtSlots];
-#pragma unroll
-        for (int j = 0; j < kVtSlots; ++j) w[j] = bp[j];
-        const int r = vt_probe(w, k, &val);
-        hit = r >= 0;
-        done = r != kVtDead;
-      }
-    }
     if (done) {
     } else if (a.dir) {
       u32x4 e[4];
@@ -655,20 +761,12 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(5))) void k
                     : ((uint64_t)pd[13 + 4 * (lo - 1)] | ((uint64_t)pd[14 + 4 * (lo - 1)] << 32));
     }
   }
-  if (a.stats) {  // wave-uniform; every lane of the wave is here
-    const uint32_t v[kIdxStats] = {wave_sum32(act && k != kKeyMax ? 1u : 0u), wave_sum32(c_int),
-                                   wave_sum32(c_right), wave_sum32(c_hops), wave_sum32(c_ent),
-                                   wave_sum32(act && val != kValueNull ? 1u : 0u),
-                                   wave_sum32(hit ? 1u : 0u)};
-    if (lane_id() == 0)
-      for (int j = 0; j < kIdxStats; ++j)
-        if (v[j]) atomicAdd(reinterpret_cast<unsigned long long*>(a.stats + j), v[j]);
-  }
+  if (a.stats) add_stats();
   if (PCHK && pv_f != pv_r) err |= kErrInconsistent;  // a torn page under a get
   if (err) atomicOr(a.err, err);
   if (act) {
-    a.out_val[i] = val;
-    if (a.out_found) a.out_found[i] = val != kValueNull ? 1 : 0;
+    a.out_val[bbase + ti] = val;
+    if (a.out_found) a.out_found[bbase + ti] = val != kValueNull ? 1 : 0;
   }
   if (a.clk && lane_id() == 0)
     a.clk[gridDim.x + blockIdx.x * (TPB / kWave) + (threadIdx.x / kWave)] = wall_clock64();
@@ -686,11 +784,23 @@ void launch_get_sum(const WalkArgs& a, uint64_t n, hipStream_t s, hipEvent_t ev0
   constexpr int TPB = kGetSumTPB;
   const uint32_t lds = (uint32_t)a.top_n * 12;
   const dim3 grid((unsigned)((n + TPB - 1) / TPB));
+  // the probe's forms matter only with a table: without one every launch is
+  // the plain instantiation (no list in LDS, no barrier)
+  const bool coop = a.vt && a.get_coop, pack = a.vt && a.get_pack;
   // ev0 / ev1 (the profile): the dispatch's own start and end
+#define SHM_GET_SUM(P, C, K) \
+  hipExtLaunchKernelGGL((k_get_sum<TPB, P, C, K>), grid, dim3(TPB), lds, s, ev0, ev1, 0u, a)
   if (a.page_check)
-    hipExtLaunchKernelGGL((k_get_sum<TPB, true>), grid, dim3(TPB), lds, s, ev0, ev1, 0u, a);
+    SHM_GET_SUM(true, false, false);
+  else if (coop && pack)
+    SHM_GET_SUM(false, true, true);
+  else if (coop)
+    SHM_GET_SUM(false, true, false);
+  else if (pack)
+    SHM_GET_SUM(false, false, true);
   else
-    hipExtLaunchKernelGGL((k_get_sum<TPB, false>), grid, dim3(TPB), lds, s, ev0, ev1, 0u, a);
+    SHM_GET_SUM(false, false, false);
+#undef SHM_GET_SUM
 }
 
 // ---- the top of the tree for the LDS replica ---------------------------------

@@ -93,6 +93,12 @@ struct WalkArgs {
   uint64_t vt_lo;
   uint64_t vt_n;
   uint32_t vt_shift;
+  // GET with a table: the probe loads each bucket line with one instruction
+  // (SHM_GET_COOP), and the gets the table does not answer are packed into
+  // the block's lowest waves (SHM_GET_PACK); 0 = the form before each (A/B,
+  // tests).  launch_get_sum picks the instantiation
+  int get_coop;
+  int get_pack;
 };
 // k_get_sum's index statistics (shm_index_stats)
 enum IdxStat {

@@ -169,6 +169,8 @@ struct shm_tree {
   bool vt_valid = false;       // built for the directory as it is, not dropped
   bool vt_on = true;           // SHM_VALTAB
   uint64_t vt_max_bytes = 8ull << 30;  // SHM_VALTAB_MAX_BYTES
+  bool get_coop = true;        // SHM_GET_COOP
+  bool get_pack = true;        // SHM_GET_PACK
   uint32_t vt_bits_failed = 64;  // an allocation this large failed: not asked again
   uint32_t vt_drop_bits = 0;   // the table was dropped at this size (too many keys in dead buckets)
   uint64_t* vt_ctr = nullptr;  // device: {dead buckets, keys in dead buckets, keys} (kVtCtrWords)
@@ -1595,6 +1597,12 @@ int shm_tree_create(const shm_config* cfg, shm_tree** out) {
     const char* v = getenv("SHM_VALTAB");
     t->vt_on = !(v && v[0] == '0');
     if (const char* m = getenv("SHM_VALTAB_MAX_BYTES")) t->vt_max_bytes = strtoull(m, nullptr, 0);
+    // SHM_GET_COOP=0 / SHM_GET_PACK=0: the get's probe and fall-through in
+    // the form before each (A/B; kernels.h WalkArgs)
+    const char* c = getenv("SHM_GET_COOP");
+    t->get_coop = !(c && c[0] == '0');
+    const char* p = getenv("SHM_GET_PACK");
+    t->get_pack = !(p && p[0] == '0');
   }
   auto fail = [&](int rc) {
     free_all(t);
@@ -1778,6 +1786,8 @@ static int search_impl(shm_tree* t, hipStream_t s, Order& ord, const uint64_t* k
       a.vt_lo = t->cfg.key_lo;
       a.vt_shift = t->cfg.key_bits - t->vt_bits;
       a.vt_n = 1ull << t->vt_bits;
+      a.get_coop = t->get_coop ? 1 : 0;
+      a.get_pack = t->get_pack ? 1 : 0;
     }
     if (use_top(t) && t->top_valid) {
       a.top_keys = t->top_keys;
@@ -2437,6 +2447,17 @@ int shm__dir_config(shm_tree* t, int maint, uint64_t mem_limit) {
   if (maint >= 0) t->dir_maint_always = maint == 2;
   if (!t->dir_maint) t->dir_exact = false;  // until the next build
   t->dir_mem_limit = mem_limit;
+  return SHM_OK;
+}
+
+// test hook: the get's forms for this tree's later launches (as SHM_GET_COOP /
+// SHM_GET_PACK set them at its creation; < 0: as is), so one tree's state can
+// be read in every form
+int shm__get_forms(shm_tree* t, int coop, int pack) {
+  if (!t) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  if (coop >= 0) t->get_coop = coop != 0;
+  if (pack >= 0) t->get_pack = pack != 0;
   return SHM_OK;
 }
 

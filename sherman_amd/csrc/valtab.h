@@ -54,16 +54,29 @@ __host__ __device__ __forceinline__ bool vt_bucket_of(uint64_t lo, uint32_t shif
   return p < n;
 }
 
-// the get's probe of a bucket it loaded whole (w: 8 x (key lo, key hi, value
-// lo, value hi)): the dead marker first, then the live slot holding k
+// The probe's per-slot predicates (w: one slot as key lo, key hi, value lo,
+// value hi), shared by the lane that loads a whole bucket (vt_probe) and the
+// eight lanes that load one slot each (get.hip's cooperative probe).
+// slot 0 carries the dead marker
+__device__ __forceinline__ bool vt_slot_dead(const u32x4& w) {
+  return (w.x & w.y) == 0xFFFFFFFFu;
+}
+// a live slot holding k; *sv = the slot's value either way
+__device__ __forceinline__ bool vt_slot_match(const u32x4& w, uint64_t k, uint64_t* sv) {
+  const uint64_t sk = (uint64_t)w.x | ((uint64_t)w.y << 32);
+  *sv = (uint64_t)w.z | ((uint64_t)w.w << 32);
+  return sk == k && *sv != kValueNull;
+}
+
+// the get's probe of a bucket it loaded whole (w: 8 slots): the dead marker
+// first, then the highest live slot holding k
 __device__ __forceinline__ int vt_probe(const u32x4 (&w)[kVtSlots], uint64_t k, uint64_t* val) {
-  if ((w[0].x & w[0].y) == 0xFFFFFFFFu) return kVtDead;
+  if (vt_slot_dead(w[0])) return kVtDead;
   int r = kVtAbsent;
 #pragma unroll
   for (int j = 0; j < kVtSlots; ++j) {
-    const uint64_t sk = (uint64_t)w[j].x | ((uint64_t)w[j].y << 32);
-    const uint64_t sv = (uint64_t)w[j].z | ((uint64_t)w[j].w << 32);
-    if (sk == k && sv != kValueNull) {
+    uint64_t sv;
+    if (vt_slot_match(w[j], k, &sv)) {
       *val = sv;
       r = j;
     }
