@@ -138,7 +138,30 @@ int shm_search_batch(shm_tree *t, const uint64_t *keys, uint64_t n,
  * chunks, before and after it, are applied), SHM_ENOMEM if the arena ran out
  * (the splits that did not fit are left unapplied), SHM_EIO on a device fault
  * or a tree inconsistency the kernels detected (shm_last_error names the
- * bits and the chunk that first saw them).  A chunk whose split propagation
+ * bits and the chunk that first saw them).
+ * After SHM_ENOMEM (tests/test_gpu_arena_full.py):
+ *  - A leaf whose split did not fit keeps every entry it had: all ops of the
+ *    chunk that fall inside its fences (new keys and overwrites alike) are
+ *    left unapplied, together.  Every other op of the chunk is applied, the
+ *    deletes included (they run after the splits).  So each key is either as
+ *    it was before the chunk or as the whole chunk would have left it.
+ *  - The pages of a split are not taken all at once: when the leaf level
+ *    fitted and an internal level did not, the new pages exist, hold their
+ *    keys and are reached through their left sibling alone (their separator
+ *    is missing one level up, and stays missing).  That is a legal B-link
+ *    state, which every reader follows and shm_check accepts; the allocation
+ *    was not made all-or-nothing for a whole path.
+ *  - Every reader (gets by any path: bucket table, directory, summary or
+ *    page walk; scans, lower bounds, range queries) answers what the pages
+ *    hold, also a get queued behind the failing chunk before the host has
+ *    seen the status: the chunk's directory and table upkeep reads what the
+ *    tree did when the device error word holds the bit.
+ *  - The handle stays usable: ops that need no new page (overwrites,
+ *    deletes, new keys in leaves with room) return SHM_OK, a chunk that needs
+ *    a page returns SHM_ENOMEM again.  pages_used never exceeds
+ *    pages_capacity; a failed take counts the free pages that were left
+ *    (fewer than it asked for) as used, so those are lost to later chunks.
+ * A chunk whose split propagation
  * gave up waiting (a hand-off bound) is completed in the same launch by its
  * last block alone, before any later call reads the tree (counted in
  * shm_error_t.resumed; not an error), as the reference always completes a

@@ -27,7 +27,12 @@
 //     the repair write the form, and a key the chunk updated in place or
 //     deleted lists its entry for the repair (dir_note_changed).  Here the
 //     upkeep IS about results: a chunk that skips it ends the directory's
-//     exactness (tree.cpp), and the gets then ignore the form.
+//     exactness (tree.cpp), and the gets then ignore the form;
+//   * when the arena ran out (kErrNoMem in the device error word, final
+//     once k_upper is done) a split segment whose page still has the front
+//     version the upsert kernel read was left unapplied: its page is no split
+//     page (any slot order) and its entries stay as they are, and the bucket
+//     table takes each op key's pair from the tree instead of from the op.
 // Every entry a get trusts still only names slots to read: a get that does
 // not find its key there walks the summary path (get.hip), so the upkeep is
 // about cost, never about results.  Prefixes of a split page without keys

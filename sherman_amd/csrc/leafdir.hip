@@ -605,6 +605,39 @@ __global__ __launch_bounds__(256) void k_dir_repair(const uint8_t* __restrict__ 
   }
 }
 
+// Key k's value as the tree holds it now, one wave (false: not stored): the
+// header walk from the root with page_search's sibling rule (Tree.cpp:
+// 593-663), then the leaf's slots, one per lane.  For a tree nobody writes
+// (after the chunk's k_upper).
+__device__ __forceinline__ bool tree_pair(const UpperArgs& u, uint64_t k, uint64_t* val) {
+  const int lane = lane_id();
+  uint64_t ptr = u.root;
+  for (int hop = 0; hop < kMaxRounds && ptr_ok(ptr, u.node, u.arena_bytes); ++hop) {
+    const u32x4 w = load_page_slice(u.arena, ga_offset(ptr));
+    const Hdr h = parse_hdr(w);
+    if (k >= h.highest && h.sibling != 0) {
+      ptr = h.sibling;
+      continue;
+    }
+    if (k < h.lowest || k >= h.highest) return false;
+    if (h.leftmost != 0) {
+      const IntRec r = internal_record(w);
+      const int cnt = h.last_index + 1;
+      const int pos = popc64(ballot(lane >= 3 && lane - 3 < cnt && r.key <= k));
+      ptr = pos == 0 ? h.leftmost : rl64(r.ptr, pos + 2);
+      continue;
+    }
+    uint64_t ek = 0, ev = 0;
+    uint32_t f = 0, r = 0;
+    if (lane < kLeafCardinality) lane_entry(u.arena + ga_offset(ptr), lane, ek, ev, f, r);
+    const uint64_t m = ballot(lane < kLeafCardinality && entry_hit(ek, ev, f, r, k));
+    if (!m) return false;
+    *val = rl64(ev, ctz64(m));
+    return true;
+  }
+  return false;
+}
+
 // The chunk's directory upkeep, after its k_upper (round 6; dir_upkeep.h):
 // one wave per staged segment of the chunk (the leaves that got a new key).
 // A segment applied in place: each new key's pair / fingerprint goes into
@@ -623,6 +656,10 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
   // the value form also follows the keys changed in place and the deletes
   const bool vals = u.dir_vals && u.dir_form == kDirFormPairs;
   const uint64_t n_del = (vals || u.vt) && u.n_del ? *u.n_del : 0;
+  // every writer of the chunk has finished: its error bits are final
+  const bool nomem =
+      (__hip_atomic_load(u.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kErrNoMem) != 0;
+  const bool unapplied = u.vt && nomem;
   uint64_t n_all = n_ops > ns ? n_ops : (uint64_t)ns;
   if (n_del > n_all) n_all = n_del;
   const uint64_t nwin = (n_all + kWave - 1) / kWave;
@@ -644,11 +681,29 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
     }
     if (i < n_del && vals) dir_note_changed(u, u.dk[i]);
     // the bucket table follows every op of the chunk, whatever the tree did
-    // with it (placed, updated in place, split): it is independent of leaves
+    // with it (placed, updated in place, split): it is independent of leaves.
+    // Unless the arena ran out (kErrNoMem: this chunk, or an earlier one
+    // whose status the host has not read yet): a split that did not fit left
+    // its segment's ops unapplied, so each op's key then takes the pair the
+    // tree holds for it now, read key by key by the whole wave
     if (u.vt) {
       uint64_t b;
       uint32_t killed = 0;
-      if (i < n_ops && vt_bucket_of(u.vt_lo, u.vt_shift, u.vt_n, u.op_key[i], &b)) {
+      const bool op = i < n_ops && vt_bucket_of(u.vt_lo, u.vt_shift, u.vt_n, u.op_key[i], &b);
+      if (unapplied) {
+        const uint64_t mine = op ? u.op_key[i] : 0ull;
+        uint64_t v = kValueNull;
+        for (uint64_t m = ballot(op); m; m &= m - 1) {
+          const int l = ctz64(m);
+          uint64_t tv = kValueNull;
+          const bool held = tree_pair(u, rl64(mine, l), &tv);
+          if (lane == l) v = held ? tv : kValueNull;
+        }
+        if (op && v == kValueNull)
+          vt_delete(u.vt + kVtBucketWords * b, u.op_key[i]);
+        else if (op)
+          killed = vt_upsert(u.vt + kVtBucketWords * b, u.op_key[i], v) == kVtKilled ? 1u : 0u;
+      } else if (op) {
         const uint64_t v = u.op_val[i];
         if (v == kValueNull)
           vt_delete(u.vt + kVtBucketWords * b, u.op_key[i]);
@@ -673,6 +728,11 @@ __global__ __launch_bounds__(256) void k_dir_upkeep(UpperArgs u, const uint32_t*
       const uint32_t P = u.seg_P[gs];
       uint64_t page = u.seg_page[gs];
       if (!ptr_ok(page, u.node, u.arena_bytes)) continue;
+      // the arena ran out: a split that did not fit left its page as the
+      // upsert kernel read it (a split's page 0, and a root that grew, move
+      // the front version on), in any slot order, and its entries as they are
+      if (nomem && parse_hdr(load_page_slice(u.arena, ga_offset(page))).fver == u.seg_ver[gs])
+        continue;
       // page 0 is the segment's page, unless that page became the root's
       // internal page (the root grew: its left half is the leftmost; a root
       // leaf split into more pages than one internal page holds grew twice

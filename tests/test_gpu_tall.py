@@ -33,6 +33,7 @@ torch = pytest.importorskip("torch")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import dir_model  # noqa: E402
+from arena_model import hot_chunk  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
@@ -240,25 +241,6 @@ def test_readers_on_a_tall_tree(lib_ok, root_level, path, kind):
     assert t.stats()["height"] == root_level + 1
     orc.close()
     t.close()
-
-
-def hot_chunk(info):
-    """40 absent keys inside the hot leaf's fences, 10 deletes and 10
-    overwrites of keys in thin leaves elsewhere, and two in-chunk duplicates
-    (a new key written twice, an overwritten key written again): keys,
-    values (0 deletes; the last writer of a key wins)."""
-    k = info["keys"]
-    inside = (k >= U64(info["hot_lo"])) & (k < U64(info["hot_hi"]))
-    hot, thin = k[inside], k[~inside]
-    assert hot.size == ib.FULL_KEYS
-    new = hot[:40] + U64(7)
-    far = thin[np.linspace(0, thin.size - 1, 20).astype(np.int64)]
-    dele, over = far[::2], far[1::2]
-    keys = np.concatenate([new[:20], dele, over, new[20:], new[3:4], over[5:6]])
-    vals = np.concatenate([new[:20] ^ U64(0x2222), np.zeros(10, dtype=U64), over ^ U64(0x3333),
-                           new[20:] ^ U64(0x2222), new[3:4] ^ U64(0x4444), over[5:6] ^ U64(0x5555)])
-    assert keys.size == 62 and np.unique(keys).size == 60
-    return keys, vals
 
 
 def spread_chunk(info, orc):
