@@ -22,6 +22,10 @@
  *   shm_del_batch       Tree::del(const Key&)             include/Tree.h:51,   src/Tree.cpp:542-591
  *   shm_range_query     Tree::range_query(from, to, Value*)
  *                                                         include/Tree.h:53-54, src/Tree.cpp:461-540
+ *   shm_scan_batch / shm_rscan_batch
+ *                       (no reference counterpart beyond Tree::range_query's
+ *                        traversal: ordered scans with a count limit, upwards
+ *                        and downwards)
  *   shm_stats           Tree::print_and_check_tree / index_cache_statistics
  *                                                         include/Tree.h:56, 62; src/Tree.cpp:151-203
  *   shm_dump_image / shm_load_image
@@ -265,6 +269,24 @@ int shm_range_query_slots(shm_tree *t, const uint64_t *from, const uint64_t *to,
 int shm_scan_batch(shm_tree *t, const uint64_t *from, const uint64_t *to, uint64_t n,
                    uint64_t limit, uint64_t *keys_out, uint64_t *vals_out,
                    uint64_t *counts_out, uint64_t *status_dev, void *stream);
+/* The same scans downwards (floor / predecessor, the maximum key, paging
+ * backwards): scan i returns the first min(limit, matches) valid entries with
+ * to[i] <= key <= from[i] (to == NULL: a stop of 0, no lower bound) in
+ * DESCENDING unsigned key order, keys to keys_out[i * limit ...] and values
+ * to vals_out[i * limit ...]; counts_out[i] = the number of pairs written (at
+ * most limit; == limit means there may be more: the last key - 1 is the next
+ * from, unless the last key is 0).  The rest of a scan's row is not written.
+ * to[i] > from[i] gives 0.  from[i] == kKeyMax is allowed and means "from the
+ * largest stored key" (no stored key equals kKeyMax, so unlike
+ * shm_scan_batch's from == kKeyMax it is not empty).  The leaf chain has no
+ * left links: a step to the left is a descent to the leaf holding the current
+ * leaf's lowest fence - 1 (a leaf directory entry plus the page; a descent
+ * from the root without the directory), which also follows the B-link right
+ * turns of a missing separator.  Validity, arguments, status_dev, queueing
+ * and the SHM_EINVAL cases are shm_scan_batch's. */
+int shm_rscan_batch(shm_tree *t, const uint64_t *from, const uint64_t *to, uint64_t n,
+                    uint64_t limit, uint64_t *keys_out, uint64_t *vals_out,
+                    uint64_t *counts_out, uint64_t *status_dev, void *stream);
 
 /* introspection / images (host pointers) ------------------------------------- */
 int shm_stats(shm_tree *t, shm_stats_t *out);

@@ -143,6 +143,7 @@ _SIGNATURES = [
      [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]),
     ("shm_range_query_slots", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp]),
     ("shm_scan_batch", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp]),
+    ("shm_rscan_batch", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp]),
     ("shm_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmStats)]),
     ("shm_dump_image", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     ("shm_load_image", ctypes.c_int, [vp, vp, u64, u64]),
@@ -319,12 +320,14 @@ class PendingSlots:
 
 
 class PendingScan:
-    """Result of Tree.scan_batch: (counts, keys[n, limit], vals[n, limit])
-    once the scans have run.  Scan i's pairs, in ascending unsigned key order,
-    are keys[i, :counts[i]] and vals[i, :counts[i]] (int64 bit patterns of the
-    u64 words); the rest of its row is whatever the buffers held.
-    counts[i] == limit means there may be more: keys[i, limit - 1] + 1 is the
-    next `lo`."""
+    """Result of Tree.scan_batch / Tree.rscan_batch: (counts, keys[n, limit],
+    vals[n, limit]) once the scans have run.  Scan i's pairs, in the order of
+    the call that made it (scan_batch: ascending unsigned key order,
+    rscan_batch: descending), are keys[i, :counts[i]] and vals[i, :counts[i]]
+    (int64 bit patterns of the u64 words); the rest of its row is whatever the
+    buffers held.  counts[i] == limit means there may be more: keys[i, limit -
+    1] + 1 is the next `lo` of a scan_batch, keys[i, limit - 1] - 1 the next
+    `hi` of an rscan_batch (unless that key is 0)."""
 
     def __init__(self, tree, counts, keys, vals, limit, status, done):
         n = counts.numel()
@@ -536,6 +539,41 @@ class Tree:
         k = torch.zeros(n, dtype=torch.int64, device=keys.device)
         v = torch.zeros(n, dtype=torch.int64, device=keys.device)
         c, k, v = self.scan_batch(keys, 1, stream=stream, keys=k, vals=v).result()
+        return c != 0, k.view(-1), v.view(-1)
+
+    def rscan_batch(self, hi, limit, lo=None, stream=None, keys=None, vals=None, counts=None,
+                    status=None):
+        """Descending scans with a count limit (shm_rscan_batch): scan i is
+        the first `limit` valid entries with lo[i] <= key <= hi[i] (lo None:
+        no lower bound) in descending unsigned key order; hi[i] == KEY_MAX
+        starts at the largest stored key.  Queued on `stream` without a host
+        wait.  Returns PendingScan; buffers and status as in scan_batch."""
+        import torch
+        n = hi.numel()
+        dev = hi.device
+        if lo is not None:
+            assert lo.numel() == n
+        if counts is None:
+            counts = torch.empty(n, dtype=torch.int64, device=dev)
+        if keys is None:
+            keys = torch.empty((n, limit), dtype=torch.int64, device=dev)
+        if vals is None:
+            vals = torch.empty((n, limit), dtype=torch.int64, device=dev)
+        assert keys.numel() >= n * limit and vals.numel() >= n * limit and counts.numel() >= n
+        sp = _stream_ptr(stream)
+        _check(lib().shm_rscan_batch(self.h, _ptr(hi), _ptr(lo), n, limit, _ptr(keys), _ptr(vals),
+                                     _ptr(counts), _ptr(status), sp), "rscan_batch")
+        return PendingScan(self, counts[:n], keys, vals, limit, status, _record_on(sp, dev))
+
+    def floor_batch(self, keys, stream=None):
+        """The largest stored key <= keys[i] (a descending scan with limit 1):
+        (found, key, value) tensors of n; key and value are 0 where found is
+        False (nothing at or below keys[i]).  Waits for the result."""
+        import torch
+        n = keys.numel()
+        k = torch.zeros(n, dtype=torch.int64, device=keys.device)
+        v = torch.zeros(n, dtype=torch.int64, device=keys.device)
+        c, k, v = self.rscan_batch(keys, 1, stream=stream, keys=k, vals=v).result()
         return c != 0, k.view(-1), v.view(-1)
 
     # -- reference single-op API (Tree.h:47-54) -------------------------------

@@ -8,6 +8,7 @@
 //   void del(const Key&, ...)                   del(k[, cxt, coro_id])
 //   uint64_t range_query(from, to, Value* buf)  range_query(from, to, buf[, cxt, coro_id])
 //   (new) ordered scan with a count limit       scan(from, limit, keys, vals)
+//   (new) the same downwards, predecessor       rscan(from, limit, keys, vals), floor(k, key, val)
 //   void print_and_check_tree(...)              print_and_check_tree([cxt, coro_id])
 //   void lock_bench(const Key&, ...)            lock_bench(k[, cxt, coro_id])
 //   void index_cache_statistics()               index_cache_statistics() (the leaf directory's)
@@ -138,25 +139,17 @@ class Tree {
   // keys[i] / vals[i] for i < the returned count (<= limit; == limit: there
   // may be more, keys[limit - 1] + 1 is the next from).  Host pointers.
   uint64_t scan(const Key& from, uint64_t limit, Key* keys, Value* vals) {
-    uint64_t *d_cnt = d_vals_, *d_out = nullptr;
-    if (limit == 0 || limit >= (1ull << 31)) throw Error(SHM_EINVAL, "scan limit");
-    if (hipMemcpy(d_keys_, &from, sizeof(from), hipMemcpyHostToDevice) != hipSuccess)
-      throw Error(SHM_EIO, "scan stage");
-    if (hipMalloc(&d_out, 2 * limit * sizeof(uint64_t)) != hipSuccess)
-      throw Error(SHM_ENOMEM, "scan buffers");
-    int s = shm_scan_batch(t_, d_keys_, nullptr, 1, limit, d_out, d_out + limit, d_cnt, nullptr,
-                           nullptr);
-    uint64_t cnt = 0;
-    if (s == SHM_OK && hipMemcpy(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)
-      s = SHM_EIO;
-    if (s == SHM_OK && cnt &&
-        (hipMemcpy(keys, d_out, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-         hipMemcpy(vals, d_out + limit, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost) !=
-             hipSuccess))
-      s = SHM_EIO;
-    (void)hipFree(d_out);
-    check(s, "scan");
-    return cnt;
+    return scan_dir(from, limit, keys, vals, false);
+  }
+  // The first `limit` valid entries with key <= from in descending key order
+  // (shm_rscan_batch): as scan; from == kKeyMax starts at the largest stored
+  // key, and keys[limit - 1] - 1 is the next from (unless that key is 0).
+  uint64_t rscan(const Key& from, uint64_t limit, Key* keys, Value* vals) {
+    return scan_dir(from, limit, keys, vals, true);
+  }
+  // The largest stored key <= k (an rscan of one): false when there is none.
+  bool floor(const Key& k, Key& key_out, Value& val_out) {
+    return rscan(k, 1, &key_out, &val_out) != 0;
   }
 
   // batched hot path on device pointers (see include/sherman_amd.h)
@@ -227,6 +220,27 @@ class Tree {
   const uint64_t tree_id;  // include/Tree.h:67 (one tree per handle here)
 
  private:
+  uint64_t scan_dir(const Key& from, uint64_t limit, Key* keys, Value* vals, bool descending) {
+    uint64_t *d_cnt = d_vals_, *d_out = nullptr;
+    if (limit == 0 || limit >= (1ull << 31)) throw Error(SHM_EINVAL, "scan limit");
+    if (hipMemcpy(d_keys_, &from, sizeof(from), hipMemcpyHostToDevice) != hipSuccess)
+      throw Error(SHM_EIO, "scan stage");
+    if (hipMalloc(&d_out, 2 * limit * sizeof(uint64_t)) != hipSuccess)
+      throw Error(SHM_ENOMEM, "scan buffers");
+    int s = (descending ? shm_rscan_batch : shm_scan_batch)(
+        t_, d_keys_, nullptr, 1, limit, d_out, d_out + limit, d_cnt, nullptr, nullptr);
+    uint64_t cnt = 0;
+    if (s == SHM_OK && hipMemcpy(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)
+      s = SHM_EIO;
+    if (s == SHM_OK && cnt &&
+        (hipMemcpy(keys, d_out, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+         hipMemcpy(vals, d_out + limit, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost) !=
+             hipSuccess))
+      s = SHM_EIO;
+    (void)hipFree(d_out);
+    check(s, descending ? "rscan" : "scan");
+    return cnt;
+  }
   void stage(const Key& k, const Value* v) {
     if (hipMemcpy(d_keys_, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
       throw Error(SHM_EIO, "stage key");

@@ -661,6 +661,9 @@ struct ScanArgs {
   uint64_t* status;
 };
 void launch_scan(const ScanArgs& a, hipStream_t s);
+// the same arguments read downwards (shm_rscan_batch): from = the start, to =
+// the stop (nullable: 0); pairs with to <= key <= from in descending key order
+void launch_rscan(const ScanArgs& a, hipStream_t s);
 
 // ---- host read-backs (range.hip) ------------------------------------------------
 // dst[i] = src[i] for i < nw (<= 256, dst in mapped host memory), then a

@@ -32,6 +32,9 @@
 // (k_range's order) its latency overlaps the compare and the rank, but a scan
 // that the limit ends has then read 768 B in vain, and that form measured
 // 3-5 % slower at limits 1, 10 and 100 (DESIGN.md "Ordered scans").
+//
+// k_rscan (shm_rscan_batch), below k_scan, reads the same order downwards with
+// the same helpers: its comment gives the step to the left.
 #include "device_common.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
@@ -285,7 +288,138 @@ __global__ __launch_bounds__(kScanWaves* kWave) void k_scan(ScanArgs a) {
   }
 }
 
-void launch_scan(const ScanArgs& a, hipStream_t s) {
+// Descending scans (shm_rscan_batch): scan i returns the first min(limit,
+// matches) valid entries with to[i] <= key <= from[i] in descending key order.
+// The leaf chain has no left links and needs none: a leaf's left neighbour is
+// the leaf that holds lowest - 1 (B-link fences), so a step to the left is one
+// leaf_descend(lowest - 1), a directory entry plus the page (a descent from
+// the root without the directory).  One loop, one descent per iteration with a
+// hop count of its own; the steps are bounded apart, and each step's leaf must
+// lie strictly below the last one (a corrupt image must not loop).  Inside a
+// leaf the hits are ranked by the listed keys above them; the pad word of an
+// odd count is 0, which is above no key.
+// The occupancy hint keeps k_scan's 6 waves per SIMD (80 VGPRs, no scratch):
+// left alone the allocator takes 86 and the kernel, bound by occupancy over
+// its dependent reads like k_scan, drops to 5.
+__global__ __launch_bounds__(kScanWaves* kWave) __attribute__((amdgpu_waves_per_eu(6, 6))) void
+k_rscan(ScanArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_page[kScanWaves][kRG * kPageDwords];
+  const int lane = lane_id();
+  const int wv = threadIdx.x >> 6;
+  const int q = lane / kRL, li = lane % kRL;
+  const uint64_t Q = ((uint64_t)blockIdx.x * kScanWaves + (uint64_t)wv) * kRG + (uint64_t)q;
+  const bool has = Q < a.n;
+  if (!ballot(has)) return;  // wave-uniform
+  uint32_t* lp = s_page[wv] + q * kPageDwords;
+  uint64_t* lk = reinterpret_cast<uint64_t*>(lp);  // the leaf's hit keys, once its page is unpacked
+  const uint32_t limit = a.limit;
+  uint64_t start = 0, stop = 0;
+  if (has) {
+    start = a.from[Q];
+    if (a.to) stop = a.to[Q];
+  }
+  const uint64_t row = Q * (uint64_t)limit;  // the scan's row (written only for has, below limit)
+  uint32_t err = 0;
+  uint32_t cnt = 0;
+  bool act = has && stop <= start;
+  // the key whose leaf comes next, and the bound of that leaf's hits: the
+  // start, then each leaf's lowest fence - 1.  No stored key equals kKeyMax,
+  // and the last leaf holds kKeyMax - 1
+  uint64_t cur = start == kKeyMax ? kKeyMax - 1 : start;
+
+  const int ebase = chunk_base<kRE>(li);
+  // every live scan of the wave takes one step per round, so the rounds
+  // count each scan's steps: wave-uniform
+  for (uint32_t steps = 0; ballot(act); ++steps) {
+    uint32_t hw = kLeafCardinality;  // slots of this leaf that may be valid
+    {
+      // the descent's last round staged the leaf in the group's slot, so the
+      // page registers end here
+      RPage w;
+      int hops = 0;  // per step: a long scan is not a long descent
+      leaf_descend(a, act, cur, lp, li, w, hops, hw, err);
+    }
+    bool left = false;  // the scan goes on to the left, if the limit allows
+    bool hit[kRE];
+    uint64_t ek[kRE], ev[kRE];
+#pragma unroll
+    for (int j = 0; j < kRE; ++j) {
+      hit[j] = false;
+      ek[j] = 0;
+      ev[j] = 0;
+    }
+    if (act) {
+      const uint64_t lowest = lds_u64(lp, 7);  // before the slot becomes the key list
+      uint32_t D[kRCD];
+      const uint32_t* ep = lp + (kOffRecords + kLeafEntry * ebase) / 4;
+#pragma unroll
+      for (int i = 0; i < kRCD; ++i) D[i] = ep[i];
+      uint32_t ef[kRE], er[kRE];
+      chunk_entries<kRE>(D, ek, ev, ef, er);
+#pragma unroll
+      for (int j = 0; j < kRE; ++j)
+        hit[j] = ebase + j >= li * kRE && (uint32_t)(ebase + j) < hw && ev[j] != kValueNull &&
+                 ((ef[j] ^ er[j]) & 0xF) == 0 && ek[j] >= stop && ek[j] <= cur;
+      if (lowest > cur) {
+        // cur is the last leaf's lowest fence - 1 (or the start): this leaf
+        // does not lie at or below it, the step did not move left
+        err |= kErrInconsistent;
+      } else {
+        left = lowest > stop && lowest != 0;
+        cur = lowest - 1;
+      }
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < kRE; ++j) c += hit[j] ? 1u : 0u;
+    uint32_t tot;  // <= kLeafCardinality: every slot has one owner lane
+    uint32_t idx = group_scan(c, li, &tot);
+    wave_lds_sync();  // the page is in registers: its slot becomes the key list
+#pragma unroll
+    for (int j = 0; j < kRE; ++j)
+      if (hit[j]) lk[idx++] = ek[j];
+    if (li == 0 && (tot & 1u)) lk[tot] = 0;  // pads the last pair: above no key
+    wave_lds_sync();
+    uint32_t r[kRE] = {0, 0, 0, 0};
+#pragma unroll 1  // as k_scan: unrolled, its loads in flight cost a wave per SIMD
+    for (uint32_t m = 0; m < tot; m += 2) {
+      const u64x2 km = *reinterpret_cast<const u64x2*>(lk + m);
+#pragma unroll
+      for (int j = 0; j < kRE; ++j)
+        r[j] += (km.x > ek[j] ? 1u : 0u) + (km.y > ek[j] ? 1u : 0u);
+    }
+    uint32_t rs = 0;
+#pragma unroll
+    for (int j = 0; j < kRE; ++j) {
+      if (hit[j]) {
+        rs += r[j];
+        const uint32_t pos = cnt + r[j];
+        if (pos < limit) {
+          a.keys[row + pos] = ek[j];
+          a.vals[row + pos] = ev[j];
+        }
+      }
+    }
+    uint32_t rt;
+    (void)group_scan(rs, li, &rt);
+    if (rt * 2u != tot * (tot - 1u)) err |= kErrInconsistent;  // equal keys in one leaf
+    cnt = cnt + tot < limit ? cnt + tot : limit;
+    wave_lds_sync();  // LDS reads done before the next descent stages
+    if (act && left && cnt < limit && steps >= (1u << 24)) {
+      err |= kErrBadPtr;
+      left = false;
+    }
+    act = act && left && cnt < limit;
+  }
+  if (has && li == 0) a.counts[Q] = cnt;
+  if (err) {
+    atomicOr(a.err, err);
+    if (a.status) atomicOr(reinterpret_cast<unsigned long long*>(a.status + 1), (unsigned long long)err);
+  }
+}
+
+namespace {
+void launch_pieces(void (*kernel)(ScanArgs), const ScanArgs& a, hipStream_t s) {
   const uint64_t per = (uint64_t)kScanWaves * kRG;
   // a grid holds fewer than 2^31 blocks: longer batches in pieces
   const uint64_t piece = per << 26;
@@ -298,9 +432,13 @@ void launch_scan(const ScanArgs& a, hipStream_t s) {
     b.vals = a.vals + off * (uint64_t)a.limit;
     b.counts = a.counts + off;
     const dim3 grid((unsigned)((b.n + per - 1) / per)), block(kScanWaves * kWave);
-    hipLaunchKernelGGL(k_scan, grid, block, 0, s, b);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, b);
   }
 }
+}  // namespace
+
+void launch_scan(const ScanArgs& a, hipStream_t s) { launch_pieces(k_scan, a, s); }
+void launch_rscan(const ScanArgs& a, hipStream_t s) { launch_pieces(k_rscan, a, s); }
 
 }  // namespace dev
 }  // namespace shm

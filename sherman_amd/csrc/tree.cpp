@@ -2113,9 +2113,12 @@ int shm_range_query_slots(shm_tree* t, const uint64_t* from, const uint64_t* to,
   return range_launch(t, s, a);
 }
 
-int shm_scan_batch(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n,
-                   uint64_t limit, uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out,
-                   uint64_t* status_dev, void* stream) {
+namespace {
+// shm_scan_batch and shm_rscan_batch: one argument check, one queueing, the
+// kernel by direction
+int scan_call(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n, uint64_t limit,
+              uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out, uint64_t* status_dev,
+              void* stream, bool descending) {
   // the arguments first: a rejected call uses neither the handle nor the GPU
   if (limit == 0 || limit >= (1ull << 31)) return SHM_EINVAL;
   if (n && (!from || !keys_out || !vals_out || !counts_out)) return SHM_EINVAL;
@@ -2147,13 +2150,31 @@ int shm_scan_batch(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64
   if (t->prof_on) {
     if (const int rc = prof_begin(t, s, shm_tree::kProfRange, n, 2, pr)) return rc;
   }
-  dev::launch_scan(a, s);
+  if (descending)
+    dev::launch_rscan(a, s);
+  else
+    dev::launch_scan(a, s);
   HIP_OK(hipGetLastError());
   if (t->prof_on) {
     HIP_OK(hipEventRecord(pr.e[1], s));
     t->prof_pending.push_back(pr);
   }
   return SHM_OK;
+}
+}  // namespace
+
+int shm_scan_batch(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n,
+                   uint64_t limit, uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out,
+                   uint64_t* status_dev, void* stream) {
+  return scan_call(t, from, to, n, limit, keys_out, vals_out, counts_out, status_dev, stream,
+                   false);
+}
+
+int shm_rscan_batch(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n,
+                    uint64_t limit, uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out,
+                    uint64_t* status_dev, void* stream) {
+  return scan_call(t, from, to, n, limit, keys_out, vals_out, counts_out, status_dev, stream,
+                   true);
 }
 
 // Library-internal, not part of include/sherman_amd.h (shard.cpp): a routed
