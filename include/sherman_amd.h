@@ -26,6 +26,9 @@
  *                       (no reference counterpart beyond Tree::range_query's
  *                        traversal: ordered scans with a count limit, upwards
  *                        and downwards)
+ *   shm_bulk_plan / shm_bulk_load
+ *                       (no reference counterpart: the reference fills a tree
+ *                        by Tree::insert alone, test/benchmark.cpp:150-158)
  *   shm_stats           Tree::print_and_check_tree / index_cache_statistics
  *                                                         include/Tree.h:56, 62; src/Tree.cpp:151-203
  *   shm_dump_image / shm_load_image
@@ -298,6 +301,52 @@ int shm_dump_image(shm_tree *t, void *host_buf, uint64_t cap,
  * (pages at GlobalAddress offsets, nodeID == cfg.node_id). */
 int shm_load_image(shm_tree *t, const void *host_buf, uint64_t bytes,
                    uint64_t root_ptr);
+/* Bulk load: the tree of a sorted run of pairs, written in one pass.
+ *
+ * shm_bulk_plan is the shape such a load gives, by host arithmetic alone (no
+ * handle, no GPU).  leaf_fill = entries per leaf, 1..53 (0: 36, the fill of a
+ * batched leaf split); internal_fill = records per internal page, 2..60, so
+ * children = records + 1 (0: 40); any other value is SHM_EINVAL.  Level 0 has
+ * P0 = ceil(n / leaf_fill) leaves (n == 0: one empty leaf, the tree of
+ * shm_tree_create), level l >= 1 has ceil(P(l-1) / (internal_fill + 1)) pages,
+ * and the first level with a single page is the root; a root above level 7
+ * (kMaxLevelOfTree) is SHM_EINVAL.  Every level deals the C items below it
+ * (pairs for leaves, children above) over its P pages evenly: with q = C / P
+ * and r = C % P, page p takes items [p q + min(p, r), (p + 1) q + min(p + 1,
+ * r)), so every internal page has at least two children. */
+typedef struct shm_bulk_plan_t {
+  uint64_t pages;          /* tree pages the load writes (root included, superblock not) */
+  uint32_t root_level;     /* 0..7 */
+  uint32_t reserved;
+  uint64_t level_pages[8]; /* pages of level 0..root_level, 0 above */
+} shm_bulk_plan_t;
+int shm_bulk_plan(uint64_t n, uint32_t leaf_fill, uint32_t internal_fill,
+                  shm_bulk_plan_t *out);
+/* Replace the tree's contents with the n pairs (keys[i], vals[i]): DEVICE
+ * pointers, keys strictly ascending (unsigned); sorting is the caller's.
+ * The tree has the shape of shm_bulk_plan(n, leaf_fill, internal_fill) at
+ * fixed places: the root is page 1 (also after a shm_load_image that put it
+ * elsewhere); below a root that is not a leaf, level 0 occupies pages 2 ..
+ * 2 + P0 - 1 in key order, then level 1, and so on; shm_stats' pages_used ==
+ * plan.pages afterwards.  Every page is written whole (lock word 0, versions
+ * 1, sibling = the next page of its level, lowest fence = the first key under
+ * it, 0 for a level's first page, highest = the next page's lowest, kKeyMax for
+ * the last; a leaf's entries in slots 0 .. count - 1 in key order), so nothing
+ * of the earlier tree survives in a reused page; the leaf directory and what
+ * is built with it are dropped and rebuilt by the next reader.
+ * Checked before anything is written, the tree staying exactly as it was:
+ * SHM_EINVAL for keys[i] >= keys[i + 1], a key == kKeyMax or a value ==
+ * kValueNull (one pass on the device), for a null handle, null keys / vals
+ * with n > 0, a leaf_fill / internal_fill out of range, a plan that is too
+ * tall, or an outstanding shm_insert_order ticket; SHM_ENOMEM when
+ * plan.pages + 1 exceeds the arena's pages.  Rejected arguments return before
+ * the handle is used.
+ * Exclusive and synchronising, like shm_load_image: it runs after everything
+ * queued before it on any stream and returns when the tree is complete.  n is
+ * not bounded by cfg.max_batch. */
+int shm_bulk_load(shm_tree *t, const uint64_t *keys, const uint64_t *vals,
+                  uint64_t n, uint32_t leaf_fill, uint32_t internal_fill,
+                  void *stream);
 /* Structural check on device data: fences, ordering, occupancy. */
 int shm_check(shm_tree *t, uint64_t *n_leaves, uint64_t *n_internal,
               uint64_t *n_keys);

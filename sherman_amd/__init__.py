@@ -73,6 +73,10 @@ class ShmStats(ctypes.Structure):
     ]
 
 
+class ShmBulkPlan(ctypes.Structure):
+    _fields_ = [("pages", u64), ("root_level", u32), ("reserved", u32), ("level_pages", u64 * 8)]
+
+
 class ShermanError(RuntimeError):
     def __init__(self, rc, what=""):
         self.rc = rc
@@ -147,6 +151,8 @@ _SIGNATURES = [
     ("shm_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmStats)]),
     ("shm_dump_image", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     ("shm_load_image", ctypes.c_int, [vp, vp, u64, u64]),
+    ("shm_bulk_plan", ctypes.c_int, [u64, u32, u32, ctypes.POINTER(ShmBulkPlan)]),
+    ("shm_bulk_load", ctypes.c_int, [vp, vp, vp, u64, u32, u32, vp]),
     ("shm_check", ctypes.c_int, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     ("shm_synchronize", ctypes.c_int, [vp]),
     ("shm_read_words", ctypes.c_int, [vp, vp, u64, vp, vp]),
@@ -209,6 +215,17 @@ def lib():
 def _check(rc, what):
     if rc != SHM_OK:
         raise ShermanError(rc, what)
+
+
+def bulk_plan(n, leaf_fill=0, internal_fill=0):
+    """The shape Tree.bulk_load gives n pairs (shm_bulk_plan; host arithmetic,
+    no GPU): {"pages", "root_level", "level_pages": pages of level 0 ..
+    root_level}.  Fills out of range or a tree taller than level 7 raise
+    ShermanError(SHM_EINVAL)."""
+    p = ShmBulkPlan()
+    _check(lib().shm_bulk_plan(n, leaf_fill, internal_fill, ctypes.byref(p)), "bulk_plan")
+    return {"pages": int(p.pages), "root_level": int(p.root_level),
+            "level_pages": [int(x) for x in p.level_pages[:p.root_level + 1]]}
 
 
 def _ptr(x):
@@ -433,6 +450,20 @@ class Tree:
     def del_batch(self, keys, stream=None):
         _check(lib().shm_del_batch(self.h, _ptr(keys), keys.numel(),
                                    _stream_ptr(stream)), "del_batch")
+
+    def bulk_load(self, keys, vals, leaf_fill=0, internal_fill=0, stream=None):
+        """Replace the tree's contents with the pairs (keys[i], vals[i])
+        (shm_bulk_load): int64 device tensors holding the u64 bits, keys
+        strictly ascending as UNSIGNED numbers.  Sorting is the caller's: an
+        int64 sort puts keys >= 2^63 first (to_i64 / from_i64 convert single
+        values; sort the u64 view, e.g. in numpy, or flip the top bit around
+        a torch sort).  leaf_fill entries per leaf (0: 36), internal_fill
+        records per internal page (0: 40); the shape is bulk_plan()'s.  Waits
+        for the tree; unsorted input, KEY_MAX or a zero value raise
+        ShermanError(SHM_EINVAL) and leave the tree as it was."""
+        assert keys.numel() == vals.numel()
+        _check(lib().shm_bulk_load(self.h, _ptr(keys), _ptr(vals), keys.numel(), leaf_fill,
+                                   internal_fill, _stream_ptr(stream)), "bulk_load")
 
     def range_query_batch(self, lo, hi, stream=None):
         """Batched inclusive scans [lo_i, hi_i]: (counts, values concatenated

@@ -13,6 +13,7 @@
 //   void lock_bench(const Key&, ...)            lock_bench(k[, cxt, coro_id])
 //   void index_cache_statistics()               index_cache_statistics() (the leaf directory's)
 //   void clear_statistics()                     clear_statistics()
+//   (new) the tree of a sorted run, one pass    bulk_load(keys, vals, n[, leaf_fill, internal_fill])
 //   (new) batched forms on device pointers      search_batch / insert_batch / mixed_batch
 //
 // The coroutine arguments are accepted and ignored, so call sites of the
@@ -150,6 +151,33 @@ class Tree {
   // The largest stored key <= k (an rscan of one): false when there is none.
   bool floor(const Key& k, Key& key_out, Value& val_out) {
     return rscan(k, 1, &key_out, &val_out) != 0;
+  }
+
+  // Replace the tree's contents with n pairs, keys strictly ascending
+  // (shm_bulk_load; host pointers, copied to the device for the call).
+  // leaf_fill entries per leaf (0: 36), internal_fill records per internal
+  // page (0: 40).  False: the input was rejected (SHM_EINVAL: keys not
+  // ascending, kKeyMax, a kValueNull value, fills out of range, a tree taller
+  // than level 7) and the tree is as it was; other failures throw.
+  bool bulk_load(const Key* keys, const Value* vals, uint64_t n, uint32_t leaf_fill = 0,
+                 uint32_t internal_fill = 0) {
+    uint64_t *d_k = nullptr, *d_v = nullptr;
+    int s = SHM_OK;
+    if (n) {
+      if (!keys || !vals) return false;
+      if (hipMalloc(&d_k, n * sizeof(uint64_t)) != hipSuccess ||
+          hipMalloc(&d_v, n * sizeof(uint64_t)) != hipSuccess)
+        s = SHM_ENOMEM;
+      else if (hipMemcpy(d_k, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(d_v, vals, n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+        s = SHM_EIO;
+    }
+    if (s == SHM_OK) s = shm_bulk_load(t_, d_k, d_v, n, leaf_fill, internal_fill, nullptr);
+    if (d_k) (void)hipFree(d_k);
+    if (d_v) (void)hipFree(d_v);
+    if (s == SHM_EINVAL) return false;
+    check(s, "bulk_load");
+    return true;
   }
 
   // batched hot path on device pointers (see include/sherman_amd.h)

@@ -1,6 +1,7 @@
 // kernels.h — launch interface between the host runtime (tree.cpp) and the
 // HIP kernels (get.hip, locate.hip, isort.hip, partition.hip, upsert.hip,
-// insert.hip, leafdir.hip, range.hip, scan.hip, util.hip).  Host-only types; no torch.
+// insert.hip, leafdir.hip, range.hip, scan.hip, bulk.hip, util.hip).  Host-only types; no
+// torch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -664,6 +665,47 @@ void launch_scan(const ScanArgs& a, hipStream_t s);
 // the same arguments read downwards (shm_rscan_batch): from = the start, to =
 // the stop (nullable: 0); pairs with to <= key <= from in descending key order
 void launch_rscan(const ScanArgs& a, hipStream_t s);
+
+// ---- bulk load (bulk.hip) -------------------------------------------------------
+// Every level deals its C items (pairs for leaves, children above) over its
+// pages evenly: q = C / pages each, one more for the first r = C % pages.
+// status |= 1 unless keys[0, n) strictly ascend (so none is kKeyMax but
+// possibly the last, which is rejected too) and no value is kValueNull
+void launch_bulk_check(const uint64_t* keys, const uint64_t* vals, uint64_t n, uint32_t* status,
+                       hipStream_t s);
+// the leaves: leaf p is arena page page0 + p (whole page, summary line,
+// leaf_hw byte), its sibling the next page, 0 for the last
+struct BulkLeafArgs {
+  uint8_t* arena;
+  uint16_t node;
+  const uint64_t* keys;
+  const uint64_t* vals;
+  uint64_t pages;  // >= 1 (one empty leaf for no pairs)
+  uint64_t q, r;
+  uint64_t page0;
+  uint8_t* sum;
+  uint8_t* leaf_hw;
+};
+void launch_bulk_leaves(const BulkLeafArgs& a, hipStream_t s);
+// one internal level: page p is arena page page0 + p, its children the pages
+// child0 + c of the level below.  A child's lowest fence comes from low_in[c]
+// (what the level below wrote to its low_out), or with low_in == nullptr
+// (level 1) from keys[] by the leaves' deal (leaf_q, leaf_r); child 0's is 0
+struct BulkLevelArgs {
+  uint8_t* arena;
+  uint16_t node;
+  uint32_t level;
+  const uint64_t* keys;
+  uint64_t leaf_q, leaf_r;
+  const uint64_t* low_in;
+  uint64_t* low_out;  // nullable (the root)
+  uint64_t pages;
+  uint64_t q, r;
+  uint64_t page0, child0;
+  uint8_t* sum;
+  uint8_t* leaf_hw;
+};
+void launch_bulk_level(const BulkLevelArgs& a, hipStream_t s);
 
 // ---- host read-backs (range.hip) ------------------------------------------------
 // dst[i] = src[i] for i < nw (<= 256, dst in mapped host memory), then a

@@ -93,6 +93,10 @@ struct shm_tree {
   uint32_t *seg_T = nullptr, *seg_P = nullptr, *seg_np = nullptr, *seg_ver = nullptr;
   uint8_t* leaf_hw = nullptr;   // per-page occupancy bound (layout.h kLeafHwFull)
   uint8_t* sum = nullptr;       // leaf summaries, kSumBytes per page (layout.h)
+  // shm_bulk_load: the lowest fences of the internal levels below the root,
+  // one array per level (bulk.hip k_bulk_level); grown on demand
+  uint64_t* bulk_low = nullptr;
+  uint64_t bulk_low_words = 0;
   // upsert staging verdicts: per op the slot it overwrites (k_locate), per
   // page the last chunk tag that brought it a new key
   uint32_t* oslot = nullptr;
@@ -1352,7 +1356,7 @@ void free_all(shm_tree* t) {
   F(t->ka); F(t->kb); F(t->ia); F(t->ib); F(t->ic); F(t->kc); F(t->id); F(t->part_mx); F(t->part_mt);
   F(t->uk); F(t->uv); F(t->dk); F(t->pages); F(t->seg_lb); F(t->bsum64);
   F(t->seg_start); F(t->seg_end); F(t->seg_page); F(t->seg_T); F(t->seg_P); F(t->seg_np);
-  F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->oslot); F(t->pnew);
+  F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->bulk_low); F(t->oslot); F(t->pnew);
   F(t->ctl); F(t->leaf_rd); F(t->dir_fix); F(t->dir_fix_n); F(t->vt); F(t->vt_ctr);
   for (int i = 0; i < 2; ++i) { F(t->sep_key[i]); F(t->sep_ptr[i]); F(t->ipage[i]); }
   F(t->h_end); F(t->h_T); F(t->h_P); F(t->h_ver); F(t->h_lk);
@@ -2374,6 +2378,141 @@ int shm_load_image(shm_tree* t, const void* host_buf, uint64_t bytes,
   t->top_valid = false;
   Order ord(t, t->stream, true);
   return write_superblock(t, t->stream);
+}
+
+// The shape of a bulk-loaded tree: P0 = ceil(n / leaf_fill) leaves (one empty
+// leaf for n == 0), ceil(P / (internal_fill + 1)) pages on each level above,
+// the first level with one page the root.  Every level deals the C items
+// below it over its P pages evenly (C / P each, one more for the first C % P).
+// With internal_fill >= 2 every internal page gets at least two children:
+// f = internal_fill + 1 >= 3 and P = ceil(C / f) <= (C + f - 1) / f; for
+// C <= f the one page takes all C >= 2, and for C >= f + 1 the least share
+// floor(C / P) is at least 2 because C f >= 2 (C + f - 1) follows from
+// C (f - 2) >= (f + 1)(f - 2) >= 2 f - 2, i.e. f (f - 3) >= 0.
+int shm_bulk_plan(uint64_t n, uint32_t leaf_fill, uint32_t internal_fill, shm_bulk_plan_t* out) {
+  if (!out) return SHM_EINVAL;
+  const uint64_t lf = leaf_fill ? leaf_fill : (uint32_t)kLeafSplitFill;
+  const uint64_t inf = internal_fill ? internal_fill : (uint32_t)kInternalSplitFill;
+  if (lf > (uint64_t)(kLeafCardinality - 1) || inf < 2 || inf > (uint64_t)(kInternalCardinality - 1))
+    return SHM_EINVAL;
+  shm_bulk_plan_t p{};
+  uint64_t pages = n / lf + (n % lf ? 1 : 0);
+  if (pages == 0) pages = 1;
+  uint32_t level = 0;
+  for (;; ++level) {
+    if (level > (uint32_t)kMaxLevelOfTree) return SHM_EINVAL;
+    p.level_pages[level] = pages;
+    p.pages += pages;
+    if (pages == 1) break;
+    pages = pages / (inf + 1) + (pages % (inf + 1) ? 1 : 0);
+  }
+  p.root_level = level;
+  *out = p;
+  return SHM_OK;
+}
+
+int shm_bulk_load(shm_tree* t, const uint64_t* keys, const uint64_t* vals, uint64_t n,
+                  uint32_t leaf_fill, uint32_t internal_fill, void* stream) {
+  // the arguments first: a rejected call uses neither the handle nor the GPU
+  if (n && (!keys || !vals)) return SHM_EINVAL;
+  shm_bulk_plan_t pl{};
+  if (const int rc = shm_bulk_plan(n, leaf_fill, internal_fill, &pl)) return rc;
+  if (!t) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  if (t->n_pend) return SHM_EINVAL;  // an ordered chunk waits for its apply
+  if (pl.pages + 1 > t->cap_pages) return SHM_ENOMEM;
+  hipStream_t s = pick(stream);
+  // exclusive and synchronising, as shm_load_image: after everything queued
+  // before it on any stream
+  HIP_OK(hipDeviceSynchronize());
+  mirror(t);  // exact: the device is idle
+  // word 15 of the device scratch: unused by the calls that share it (the
+  // device is idle here in any case)
+  uint32_t* status = reinterpret_cast<uint32_t*>(t->d_counts + 15);
+  if (n) {
+    // nothing is written before the input has passed
+    HIP_OK(hipMemsetAsync(status, 0, sizeof(uint32_t), s));
+    dev::launch_bulk_check(keys, vals, n, status, s);
+    HIP_OK(hipGetLastError());
+    if (const int rc = readback(t, s, status, sizeof(uint32_t))) return rc;
+    if (reinterpret_cast<const uint32_t*>(t->h_pin)[0]) return SHM_EINVAL;
+  }
+  // the lowest fences of levels 1 .. root_level - 1, one array per level
+  uint64_t low_words = 0;
+  for (uint32_t l = 1; l < pl.root_level; ++l) low_words += pl.level_pages[l];
+  if (low_words > t->bulk_low_words) {
+    uint64_t* nl = nullptr;
+    if (dalloc(&nl, low_words)) {
+      (void)hipGetLastError();
+      return SHM_ENOMEM;
+    }
+    if (t->bulk_low) (void)hipFree(t->bulk_low);
+    t->bulk_low = nl;
+    t->bulk_low_words = low_words;
+  }
+  const uint64_t old_next = t->next_page;
+  const uint64_t new_next = pl.pages + 1;
+  const uint16_t node = t->cfg.node_id;
+  // level l < root_level starts at page 2 + the pages of the levels below;
+  // the root is page 1, as at create
+  dev::BulkLeafArgs la{};
+  la.arena = t->arena;
+  la.node = node;
+  la.keys = keys;
+  la.vals = vals;
+  la.pages = pl.level_pages[0];
+  la.q = n / la.pages;
+  la.r = n % la.pages;
+  la.page0 = pl.root_level == 0 ? 1 : 2;
+  la.sum = t->sum;
+  la.leaf_hw = t->leaf_hw;
+  dev::launch_bulk_leaves(la, s);
+  uint64_t child0 = 2, low_at = 0;
+  const uint64_t* low_in = nullptr;
+  for (uint32_t l = 1; l <= pl.root_level; ++l) {
+    const uint64_t below = pl.level_pages[l - 1];
+    const bool root = l == pl.root_level;
+    dev::BulkLevelArgs a{};
+    a.arena = t->arena;
+    a.node = node;
+    a.level = l;
+    a.keys = keys;
+    a.leaf_q = la.q;
+    a.leaf_r = la.r;
+    a.low_in = low_in;
+    a.low_out = root ? nullptr : t->bulk_low + low_at;
+    a.pages = pl.level_pages[l];
+    a.q = below / a.pages;
+    a.r = below % a.pages;
+    a.page0 = root ? 1 : child0 + below;
+    a.child0 = child0;
+    a.sum = t->sum;
+    a.leaf_hw = t->leaf_hw;
+    dev::launch_bulk_level(a, s);
+    low_in = a.low_out;
+    low_at += a.pages;
+    child0 += below;
+  }
+  HIP_OK(hipGetLastError());
+  // pages of the old tree past the new one keep no leaf tag
+  if (old_next > new_next)
+    HIP_OK(hipMemsetAsync(t->sum + new_next * kSumBytes, 0, (old_next - new_next) * kSumBytes, s));
+  t->root = ga_make(node, kPageSize);
+  t->root_level = pl.root_level;
+  t->next_page = new_next;
+  t->dir_valid = false;  // contents changed: rebuild the leaf directory
+  t->hint_ok = false;    // ... from the root
+  t->top_valid = false;
+  // the bucket table is trusted only beside a valid directory (vt_trusted) and
+  // the directory's next build replaces it (vt_build); dropped here as well
+  t->vt_valid = false;
+  {
+    Order ord(t, s, true);
+    if (ord.rc) return ord.rc;
+    if (const int rc = write_superblock(t, s)) return rc;
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  return SHM_OK;
 }
 
 int shm_check(shm_tree* t, uint64_t* n_leaves, uint64_t* n_internal,
