@@ -29,6 +29,10 @@
  *   shm_bulk_plan / shm_bulk_load
  *                       (no reference counterpart: the reference fills a tree
  *                        by Tree::insert alone, test/benchmark.cpp:150-158)
+ *   shm_export / shm_compact
+ *                       (no reference counterpart beyond Tree::range_query's
+ *                        traversal; the reference never frees a page,
+ *                        include/LocalAllocator.h:45-47)
  *   shm_stats           Tree::print_and_check_tree / index_cache_statistics
  *                                                         include/Tree.h:56, 62; src/Tree.cpp:151-203
  *   shm_dump_image / shm_load_image
@@ -347,6 +351,54 @@ int shm_bulk_plan(uint64_t n, uint32_t leaf_fill, uint32_t internal_fill,
 int shm_bulk_load(shm_tree *t, const uint64_t *keys, const uint64_t *vals,
                   uint64_t n, uint32_t leaf_fill, uint32_t internal_fill,
                   void *stream);
+/* Sorted export: every valid pair with lo <= key <= hi in ascending unsigned
+ * key order, in parallel passes on the device.  The result is exactly the
+ * pairs, and the order, that shm_scan_batch(from = lo, to = hi) with an
+ * unbounded limit would return: Tree::range_query's traversal (the leaf
+ * holding lo, then the sibling chain; src/Tree.cpp:461-540) and validity rule
+ * (value != kValueNull, front == rear entry version in the low nibble); pages
+ * the tree does not reach are not read as data.  lo > hi gives 0 pairs and
+ * SHM_OK; lo = 0, hi = UINT64_MAX is the whole tree (no stored key equals
+ * kKeyMax).
+ * keys_out / vals_out: DEVICE pointers; either may be NULL and that array is
+ * then not written (a keys-only export feeds splitter sampling).  With both
+ * NULL the call only counts and cap is ignored.  n_out: HOST pointer,
+ * required; it always receives the number of matching pairs.  That is the
+ * number of VALID pairs: shm_check's n_keys also counts torn entries (value
+ * != 0, versions unequal), so it may be larger.
+ * SHM_ENOSPC: a non-NULL output was given and the count exceeds cap; *n_out
+ * is set and nothing is written (the host reads the total before the write
+ * pass is launched).  Otherwise the first *n_out words of each given array
+ * are written and no word past them is touched.
+ * Ordered like shm_range_query_batch: it sees everything queued before it on
+ * any stream (e.g. an shm_insert_batch_async), and it is synchronising: it
+ * returns when the outputs are complete.  Read-only: the tree, the leaf
+ * directory, the bucket table and shm_stats stay as they were.
+ * SHM_EINVAL: null handle or null n_out (before the handle is used);
+ * SHM_ENOMEM: the workspace (48 B per allocated page, kept on the handle)
+ * could not be allocated; SHM_EIO with the scans' error bits: a bad pointer,
+ * or a walk past its bound (every chain walk and list is bounded by the
+ * allocated pages). */
+int shm_export(shm_tree *t, uint64_t lo, uint64_t hi, uint64_t *keys_out,
+               uint64_t *vals_out, uint64_t cap, uint64_t *n_out, void *stream);
+/* Compaction: rebuild the tree from its own valid pairs.  The whole tree is
+ * exported into a temporary device buffer of 16 B per pair and loaded with
+ * shm_bulk_load(leaf_fill, internal_fill) (0 / 0: the defaults 36 / 40).
+ * Afterwards the tree holds exactly the pairs it held before, in the shape of
+ * shm_bulk_plan(n_valid, leaf_fill, internal_fill) at shm_bulk_load's fixed
+ * page placement, and pages_used == plan.pages: the pages that deletes and
+ * failed splits left behind are free again.  Every consequence of a bulk load
+ * applies: entry and page versions restart at 1, the leaf directory and the
+ * bucket table are dropped and rebuilt by the next reader.  Exclusive and
+ * synchronising.
+ * Checked before the first page is written, the tree staying byte for byte as
+ * it was: SHM_EINVAL for fills out of range (before the handle is used), a
+ * null handle, a plan that is too tall for the counted pairs, or an
+ * outstanding shm_insert_order ticket; SHM_ENOMEM when the temporary buffer
+ * cannot be allocated or plan.pages + 1 exceeds the arena's pages.
+ * shm_bulk_load's own input check still runs on the exported run (about a
+ * fifth of a load): a cross-check of the export. */
+int shm_compact(shm_tree *t, uint32_t leaf_fill, uint32_t internal_fill, void *stream);
 /* Structural check on device data: fences, ordering, occupancy. */
 int shm_check(shm_tree *t, uint64_t *n_leaves, uint64_t *n_internal,
               uint64_t *n_keys);

@@ -153,6 +153,8 @@ _SIGNATURES = [
     ("shm_load_image", ctypes.c_int, [vp, vp, u64, u64]),
     ("shm_bulk_plan", ctypes.c_int, [u64, u32, u32, ctypes.POINTER(ShmBulkPlan)]),
     ("shm_bulk_load", ctypes.c_int, [vp, vp, vp, u64, u32, u32, vp]),
+    ("shm_export", ctypes.c_int, [vp, u64, u64, vp, vp, u64, ctypes.POINTER(u64), vp]),
+    ("shm_compact", ctypes.c_int, [vp, u32, u32, vp]),
     ("shm_check", ctypes.c_int, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     ("shm_synchronize", ctypes.c_int, [vp]),
     ("shm_read_words", ctypes.c_int, [vp, vp, u64, vp, vp]),
@@ -464,6 +466,47 @@ class Tree:
         assert keys.numel() == vals.numel()
         _check(lib().shm_bulk_load(self.h, _ptr(keys), _ptr(vals), keys.numel(), leaf_fill,
                                    internal_fill, _stream_ptr(stream)), "bulk_load")
+
+    def count(self, lo=0, hi=None, stream=None):
+        """The number of valid pairs with lo <= key <= hi (hi None: KEY_MAX):
+        shm_export's count pass alone.  Waits for the result."""
+        n = u64(0)
+        _check(lib().shm_export(self.h, lo, KEY_MAX if hi is None else hi, None, None, 0,
+                                ctypes.byref(n), _stream_ptr(stream)), "count")
+        return int(n.value)
+
+    def export(self, lo=0, hi=None, keys=None, vals=None, stream=None):
+        """Every valid pair with lo <= key <= hi (hi None: KEY_MAX) in
+        ascending unsigned key order (shm_export): (keys, vals), int64 device
+        tensors of length n holding the u64 bits, what one scan_batch(lo, hi)
+        with an unbounded limit would return.  keys / vals may be passed in
+        (at least n long; the slices [:n] are returned, no word past them is
+        written; with only one given, only that array is exported and the
+        other result is None), else both are allocated from a count-only
+        call.  A buffer that is too small raises ShermanError(SHM_ENOSPC) with nothing
+        written.  Read-only; waits for the result."""
+        import torch
+        hi = KEY_MAX if hi is None else hi
+        sp = _stream_ptr(stream)
+        n = u64(0)
+        if keys is None and vals is None:
+            m = self.count(lo, hi, stream)
+            keys = torch.empty(m, dtype=torch.int64, device=f"cuda:{self.device}")
+            vals = torch.empty(m, dtype=torch.int64, device=f"cuda:{self.device}")
+        cap = min(x.numel() for x in (keys, vals) if x is not None)
+        _check(lib().shm_export(self.h, lo, hi, _ptr(keys), _ptr(vals), cap, ctypes.byref(n), sp),
+               "export")
+        return (None if keys is None else keys[:n.value],
+                None if vals is None else vals[:n.value])
+
+    def compact(self, leaf_fill=0, internal_fill=0, stream=None):
+        """Rebuild the tree from its own valid pairs (shm_compact): export,
+        then bulk_load(leaf_fill, internal_fill); the shape is
+        bulk_plan(count(), leaf_fill, internal_fill).  A rejected call
+        (fills, a plan too tall or too large for the arena) raises and leaves
+        the tree as it was.  Waits for the tree."""
+        _check(lib().shm_compact(self.h, leaf_fill, internal_fill, _stream_ptr(stream)),
+               "compact")
 
     def range_query_batch(self, lo, hi, stream=None):
         """Batched inclusive scans [lo_i, hi_i]: (counts, values concatenated

@@ -14,6 +14,8 @@
 //   void index_cache_statistics()               index_cache_statistics() (the leaf directory's)
 //   void clear_statistics()                     clear_statistics()
 //   (new) the tree of a sorted run, one pass    bulk_load(keys, vals, n[, leaf_fill, internal_fill])
+//   (new) every pair of a range, in key order   export_sorted(keys, vals, cap[, lo, hi]), count([lo, hi])
+//   (new) the tree rebuilt from its own pairs   compact([leaf_fill, internal_fill])
 //   (new) batched forms on device pointers      search_batch / insert_batch / mixed_batch
 //
 // The coroutine arguments are accepted and ignored, so call sites of the
@@ -177,6 +179,45 @@ class Tree {
     if (d_v) (void)hipFree(d_v);
     if (s == SHM_EINVAL) return false;
     check(s, "bulk_load");
+    return true;
+  }
+
+  // Every valid pair with lo <= key <= hi in ascending key order (shm_export;
+  // host pointers, staged through device buffers like scan).  Returns the
+  // count; when it is above cap nothing is copied.  keys or vals may be null
+  // (that array is not exported); with both null the call only counts.
+  uint64_t export_sorted(Key* keys, Value* vals, uint64_t cap, Key lo = 0, Key hi = ~0ull) {
+    uint64_t n = 0;
+    check(shm_export(t_, lo, hi, nullptr, nullptr, 0, &n, nullptr), "export count");
+    if (n == 0 || n > cap || (!keys && !vals)) return n;
+    uint64_t* d_out = nullptr;
+    if (hipMalloc(&d_out, 2 * n * sizeof(uint64_t)) != hipSuccess)
+      throw Error(SHM_ENOMEM, "export buffers");
+    uint64_t m = 0;
+    int s = shm_export(t_, lo, hi, keys ? d_out : nullptr, vals ? d_out + n : nullptr, n, &m,
+                       nullptr);
+    if (s == SHM_OK && m != n) s = SHM_EIO;  // the tree changed between the two calls
+    if (s == SHM_OK &&
+        ((keys && hipMemcpy(keys, d_out, n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) ||
+         (vals && hipMemcpy(vals, d_out + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost) !=
+                      hipSuccess)))
+      s = SHM_EIO;
+    (void)hipFree(d_out);
+    check(s, "export");
+    return n;
+  }
+  // the number of valid pairs with lo <= key <= hi (shm_export's count pass)
+  uint64_t count(Key lo = 0, Key hi = ~0ull) { return export_sorted(nullptr, nullptr, 0, lo, hi); }
+  // Rebuild the tree from its own valid pairs (shm_compact): the shape of
+  // bulk_load(count(), leaf_fill, internal_fill), the pages deletes left behind
+  // free again.  False: rejected before anything was written (SHM_EINVAL: fills
+  // out of range, a tree taller than level 7; SHM_ENOMEM: the plan or the
+  // temporary buffer does not fit) and the tree is as it was; other failures
+  // throw.
+  bool compact(uint32_t leaf_fill = 0, uint32_t internal_fill = 0) {
+    const int s = shm_compact(t_, leaf_fill, internal_fill, nullptr);
+    if (s == SHM_EINVAL || s == SHM_ENOMEM) return false;
+    check(s, "compact");
     return true;
   }
 

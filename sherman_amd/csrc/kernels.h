@@ -1,7 +1,7 @@
 // kernels.h — launch interface between the host runtime (tree.cpp) and the
 // HIP kernels (get.hip, locate.hip, isort.hip, partition.hip, upsert.hip,
-// insert.hip, leafdir.hip, range.hip, scan.hip, bulk.hip, util.hip).  Host-only types; no
-// torch.
+// insert.hip, leafdir.hip, range.hip, scan.hip, bulk.hip, export.hip,
+// util.hip).  Host-only types; no torch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -706,6 +706,40 @@ struct BulkLevelArgs {
   uint8_t* leaf_hw;
 };
 void launch_bulk_level(const BulkLevelArgs& a, hipStream_t s);
+
+// ---- sorted export of a key range (export.hip) -----------------------------------
+// One argument block for the expansion of an internal level and for the leaf
+// passes.  A unit is (page, upper bound of the key range its parent gave it);
+// a level's list holds its units in key order.
+struct ExportArgs {
+  const uint8_t* arena;
+  uint64_t arena_bytes;
+  uint16_t node;
+  uint32_t level;            // expansion: the level of the units read (>= 1)
+  uint64_t lo, hi;           // the exported range, inclusive
+  const uint64_t* in_page;   // the units read: n of them
+  const uint64_t* in_bound;
+  uint64_t n;
+  uint64_t* cnt;             // count passes: per unit, its children / its valid pairs
+  const uint64_t* off;       // emit / write passes: the exclusive scan of cnt
+  uint64_t* out_page;        // expansion's emit pass: the units of the level below,
+  uint64_t* out_bound;       // out_cap of them at most
+  uint64_t out_cap;
+  uint64_t* keys;            // leaf write pass (either nullable): the pairs, `total`
+  uint64_t* vals;            // of them as the count pass found
+  uint64_t total;
+  uint64_t max_pages;        // allocated pages: bounds every chain walk
+  const uint8_t* leaf_hw;    // per-page occupancy bound (nullable), as in RangeArgs
+  uint32_t* err;
+};
+void launch_export_seed(uint64_t root, uint64_t* page, uint64_t* bound, hipStream_t s);
+void launch_export_expand(const ExportArgs& a, bool emit, hipStream_t s);
+void launch_export_leaf(const ExportArgs& a, bool write, hipStream_t s);
+// out = exclusive scan of in[0, n) in three launches, none waiting on another
+// block; bsum: export_scan_tiles(n) + 1 words of scratch; tot = {total, *err}
+uint64_t export_scan_tiles(uint64_t n);
+void launch_export_scan(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* bsum,
+                        uint64_t* tot, const uint32_t* err, hipStream_t s);
 
 // ---- host read-backs (range.hip) ------------------------------------------------
 // dst[i] = src[i] for i < nw (<= 256, dst in mapped host memory), then a

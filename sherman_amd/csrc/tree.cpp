@@ -97,6 +97,13 @@ struct shm_tree {
   // one array per level (bulk.hip k_bulk_level); grown on demand
   uint64_t* bulk_low = nullptr;
   uint64_t bulk_low_words = 0;
+  // shm_export: two unit lists (page, bound), counts, offsets and the scan's
+  // tile sums, each for ex_cap pages, in one allocation; grown on demand
+  uint64_t* ex_ws = nullptr;
+  uint64_t ex_cap = 0;
+  // the last count pass's leaf list (export_count -> export_write)
+  int ex_cur = 0;
+  uint64_t ex_units = 0;
   // upsert staging verdicts: per op the slot it overwrites (k_locate), per
   // page the last chunk tag that brought it a new key
   uint32_t* oslot = nullptr;
@@ -1356,7 +1363,7 @@ void free_all(shm_tree* t) {
   F(t->ka); F(t->kb); F(t->ia); F(t->ib); F(t->ic); F(t->kc); F(t->id); F(t->part_mx); F(t->part_mt);
   F(t->uk); F(t->uv); F(t->dk); F(t->pages); F(t->seg_lb); F(t->bsum64);
   F(t->seg_start); F(t->seg_end); F(t->seg_page); F(t->seg_T); F(t->seg_P); F(t->seg_np);
-  F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->bulk_low); F(t->oslot); F(t->pnew);
+  F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->bulk_low); F(t->ex_ws); F(t->oslot); F(t->pnew);
   F(t->ctl); F(t->leaf_rd); F(t->dir_fix); F(t->dir_fix_n); F(t->vt); F(t->vt_ctr);
   for (int i = 0; i < 2; ++i) { F(t->sep_key[i]); F(t->sep_ptr[i]); F(t->ipage[i]); }
   F(t->h_end); F(t->h_T); F(t->h_P); F(t->h_ver); F(t->h_lk);
@@ -2411,6 +2418,9 @@ int shm_bulk_plan(uint64_t n, uint32_t leaf_fill, uint32_t internal_fill, shm_bu
   return SHM_OK;
 }
 
+static int bulk_load_locked(shm_tree* t, const uint64_t* keys, const uint64_t* vals, uint64_t n,
+                            const shm_bulk_plan_t& pl, hipStream_t s);
+
 int shm_bulk_load(shm_tree* t, const uint64_t* keys, const uint64_t* vals, uint64_t n,
                   uint32_t leaf_fill, uint32_t internal_fill, void* stream) {
   // the arguments first: a rejected call uses neither the handle nor the GPU
@@ -2419,9 +2429,14 @@ int shm_bulk_load(shm_tree* t, const uint64_t* keys, const uint64_t* vals, uint6
   if (const int rc = shm_bulk_plan(n, leaf_fill, internal_fill, &pl)) return rc;
   if (!t) return SHM_EINVAL;
   std::lock_guard<std::mutex> g(t->mu);
+  return bulk_load_locked(t, keys, vals, n, pl, pick(stream));
+}
+
+// shm_bulk_load under t->mu, its arguments checked and its plan made
+static int bulk_load_locked(shm_tree* t, const uint64_t* keys, const uint64_t* vals, uint64_t n,
+                            const shm_bulk_plan_t& pl, hipStream_t s) {
   if (t->n_pend) return SHM_EINVAL;  // an ordered chunk waits for its apply
   if (pl.pages + 1 > t->cap_pages) return SHM_ENOMEM;
-  hipStream_t s = pick(stream);
   // exclusive and synchronising, as shm_load_image: after everything queued
   // before it on any stream
   HIP_OK(hipDeviceSynchronize());
@@ -2513,6 +2528,179 @@ int shm_bulk_load(shm_tree* t, const uint64_t* keys, const uint64_t* vals, uint6
   }
   HIP_OK(hipStreamSynchronize(s));
   return SHM_OK;
+}
+
+// ---- sorted export and compaction (export.hip) -----------------------------------
+// The export in two halves, both under t->mu on an idle device: export_count
+// runs the expansion and the leaf count pass and leaves the leaf list and its
+// offsets in the workspace; export_write is the leaf write pass over them.
+// Neither touches the tree, the directory, the bucket table or the counters.
+static int export_ws(shm_tree* t, uint64_t pages) {
+  if (pages <= t->ex_cap) return SHM_OK;
+  // headroom, so a growing tree does not reallocate at every call
+  const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(pages + pages / 4, 1024), t->cap_pages);
+  uint64_t* nw = nullptr;
+  if (dalloc(&nw, 6 * cap + dev::export_scan_tiles(cap) + 1)) {
+    (void)hipGetLastError();
+    return SHM_ENOMEM;
+  }
+  if (t->ex_ws) (void)hipFree(t->ex_ws);
+  t->ex_ws = nw;
+  t->ex_cap = cap;
+  return SHM_OK;
+}
+
+static int export_count(shm_tree* t, hipStream_t s, uint64_t lo, uint64_t hi, uint64_t* n_out) {
+  *n_out = 0;
+  t->ex_units = 0;
+  // it sees everything queued before it on any stream, and the mirror is exact
+  HIP_OK(hipDeviceSynchronize());
+  mirror(t);
+  if (lo > hi || lo == kKeyMax) return SHM_OK;  // no stored key equals kKeyMax
+  const uint64_t pages = t->next_page;
+  if (const int rc = export_ws(t, pages)) return rc;
+  const uint64_t cap = t->ex_cap;
+  uint64_t* page[2] = {t->ex_ws, t->ex_ws + cap};
+  uint64_t* bound[2] = {t->ex_ws + 2 * cap, t->ex_ws + 3 * cap};
+  uint64_t* cnt = t->ex_ws + 4 * cap;
+  uint64_t* off = t->ex_ws + 5 * cap;
+  uint64_t* bsum = t->ex_ws + 6 * cap;
+  uint64_t* tot = t->d_counts + 12;  // {total, error word}, as the range scans use it
+  dev::ExportArgs a{};
+  a.arena = t->arena;
+  a.arena_bytes = t->arena_bytes;
+  a.node = t->cfg.node_id;
+  a.lo = lo;
+  a.hi = hi;
+  a.cnt = cnt;
+  a.off = off;
+  a.out_cap = cap;
+  a.max_pages = pages;
+  a.leaf_hw = t->leaf_hw;
+  a.err = t->d_err;
+  t->err_pending = true;
+  int cur = 0;
+  uint64_t n = 1;
+  dev::launch_export_seed(t->root, page[0], bound[0], s);
+  // one step per internal level: count, scan, one read of the total, emit
+  auto counted = [&](uint64_t* total) -> int {
+    dev::launch_export_scan(cnt, off, n, bsum, tot, t->d_err, s);
+    HIP_OK(hipGetLastError());
+    if (const int rc = readback(t, s, tot, 2 * sizeof(uint64_t))) return rc;
+    *total = t->h_pin[0];
+    // bits that are no error (a resumed chunk's) are taken and the export goes on
+    return t->h_pin[1] ? check_err(t, s) : SHM_OK;
+  };
+  for (uint32_t level = t->root_level; level >= 1 && n; --level) {
+    a.level = level;
+    a.in_page = page[cur];
+    a.in_bound = bound[cur];
+    a.n = n;
+    a.out_page = page[cur ^ 1];
+    a.out_bound = bound[cur ^ 1];
+    dev::launch_export_expand(a, false, s);
+    uint64_t total = 0;
+    if (const int rc = counted(&total)) return rc;
+    if (total > cap) return SHM_EIO;  // more units than pages: not a tree
+    dev::launch_export_expand(a, true, s);
+    cur ^= 1;
+    n = total;
+  }
+  if (n == 0) return check_err(t, s);
+  a.level = 0;
+  a.in_page = page[cur];
+  a.in_bound = bound[cur];
+  a.n = n;
+  a.out_page = a.out_bound = nullptr;
+  dev::launch_export_leaf(a, false, s);
+  uint64_t total = 0;
+  if (const int rc = counted(&total)) return rc;
+  t->ex_cur = cur;
+  t->ex_units = n;
+  *n_out = total;
+  return SHM_OK;
+}
+
+// the pairs of the last export_count (lo, hi as there; total = its count)
+static int export_write(shm_tree* t, hipStream_t s, uint64_t lo, uint64_t hi, uint64_t* keys,
+                        uint64_t* vals, uint64_t total) {
+  if (t->ex_units && total) {
+    const uint64_t cap = t->ex_cap;
+    dev::ExportArgs a{};
+    a.arena = t->arena;
+    a.arena_bytes = t->arena_bytes;
+    a.node = t->cfg.node_id;
+    a.lo = lo;
+    a.hi = hi;
+    a.in_page = t->ex_ws + (uint64_t)t->ex_cur * cap;
+    a.in_bound = t->ex_ws + (2 + (uint64_t)t->ex_cur) * cap;
+    a.n = t->ex_units;
+    a.off = t->ex_ws + 5 * cap;
+    a.keys = keys;
+    a.vals = vals;
+    a.total = total;
+    a.max_pages = t->next_page;
+    a.leaf_hw = t->leaf_hw;
+    a.err = t->d_err;
+    t->err_pending = true;
+    dev::launch_export_leaf(a, true, s);
+    HIP_OK(hipGetLastError());
+  }
+  // synchronising: the outputs are complete, and the walks' error bits read
+  return check_err(t, s);
+}
+
+int shm_export(shm_tree* t, uint64_t lo, uint64_t hi, uint64_t* keys_out, uint64_t* vals_out,
+               uint64_t cap, uint64_t* n_out, void* stream) {
+  // the arguments first: a rejected call uses neither the handle nor the GPU
+  if (!n_out || !t) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  hipStream_t s = pick(stream);
+  Order ord(t, s, true);  // the export workspace; later calls follow the export
+  if (ord.rc) return ord.rc;
+  uint64_t total = 0;
+  if (const int rc = export_count(t, s, lo, hi, &total)) return rc;
+  *n_out = total;
+  const bool out = keys_out || vals_out;
+  if (out && total > cap) {
+    const int rc = check_err(t, s);
+    return rc ? rc : SHM_ENOSPC;  // nothing was written
+  }
+  return export_write(t, s, lo, hi, out ? keys_out : nullptr, out ? vals_out : nullptr,
+                      out ? total : 0);
+}
+
+int shm_compact(shm_tree* t, uint32_t leaf_fill, uint32_t internal_fill, void* stream) {
+  // the fills first: a rejected call uses neither the handle nor the GPU
+  shm_bulk_plan_t pl{};
+  if (const int rc = shm_bulk_plan(0, leaf_fill, internal_fill, &pl)) return rc;
+  if (!t) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  if (t->n_pend) return SHM_EINVAL;  // an ordered chunk waits for its apply
+  hipStream_t s = pick(stream);
+  uint64_t n = 0;
+  {
+    Order ord(t, s, true);
+    if (ord.rc) return ord.rc;
+    if (const int rc = export_count(t, s, 0, kKeyMax, &n)) return rc;
+  }
+  // everything that can fail, before the first page is written
+  int rc = shm_bulk_plan(n, leaf_fill, internal_fill, &pl);
+  if (!rc && pl.pages + 1 > t->cap_pages) rc = SHM_ENOMEM;
+  uint64_t* pairs = nullptr;
+  if (!rc && n && dalloc(&pairs, 2 * n)) {
+    (void)hipGetLastError();
+    rc = SHM_ENOMEM;
+  }
+  if (rc) {
+    const int e = check_err(t, s);
+    return e ? e : rc;
+  }
+  rc = export_write(t, s, 0, kKeyMax, pairs, pairs ? pairs + n : nullptr, n);
+  // the load's own input check runs on the exported run: a cross-check of the export
+  if (!rc) rc = bulk_load_locked(t, pairs, pairs ? pairs + n : nullptr, n, pl, s);
+  if (pairs) (void)hipFree(pairs);
+  return rc;
 }
 
 int shm_check(shm_tree* t, uint64_t* n_leaves, uint64_t* n_internal,
