@@ -399,6 +399,22 @@ int shm_export(shm_tree *t, uint64_t lo, uint64_t hi, uint64_t *keys_out,
  * shm_bulk_load's own input check still runs on the exported run (about a
  * fifth of a load): a cross-check of the export. */
 int shm_compact(shm_tree *t, uint32_t leaf_fill, uint32_t internal_fill, void *stream);
+/* Change the key range hint (cfg.key_lo / cfg.key_bits) of a live handle:
+ * afterwards the handle behaves as one created with that hint.  The hint
+ * steers the get ordering, the leaf directory and the bucket table only; keys
+ * outside it are still stored and found exactly.  It is what makes a tree of
+ * narrow keys fast: with key_bits = 64 and every key below 2^26 all keys share
+ * directory entry 0 and every get starts at the root.  key_bits == 0 is read
+ * as 64, and key_bits == 64 forces key_lo = 0, as at create.
+ * Exclusive and synchronising, ordered like shm_bulk_load: it runs after
+ * everything queued before it on any stream.  It drops exactly what
+ * shm_bulk_load drops -- the leaf directory, its level hints, the LDS replica's
+ * table and the bucket table -- and the next reader rebuilds them over the new
+ * range; the tree's pages are not touched.
+ * SHM_EINVAL: key_bits > 64 or a null handle (before the handle is used), or
+ * an outstanding shm_insert_order ticket (its chunk was ordered by the old
+ * range). */
+int shm_tree_set_key_range(shm_tree *t, uint64_t key_lo, uint32_t key_bits);
 /* Structural check on device data: fences, ordering, occupancy. */
 int shm_check(shm_tree *t, uint64_t *n_leaves, uint64_t *n_internal,
               uint64_t *n_keys);
@@ -500,7 +516,8 @@ typedef struct shm_dir_stats_t {
 int shm_dir_stats(shm_tree *t, shm_dir_stats_t *out);
 
 /* multi-GPU routing helpers (range shards: shard s owns
- * [s * 2^64 / P, (s+1) * 2^64 / P)) ------------------------------------------ */
+ * [s * 2^64 / P, (s+1) * 2^64 / P), or the range between two splitters:
+ * shm_route_bucket_bounds) ---------------------------------------------------- */
 /* Bucket n <= max_batch keys by owning shard (1 <= P <= 64): writes
  * per-shard counts[P], the keys grouped by shard into keys_out, and perm[i] =
  * source position of keys_out[i].  Stable: inside a shard, keys keep their
@@ -508,6 +525,21 @@ int shm_dir_stats(shm_tree *t, shm_dir_stats_t *out);
 int shm_route_bucket(shm_tree *t, const uint64_t *keys, uint64_t n,
                      uint32_t num_shards, uint64_t *counts_out,
                      uint64_t *keys_out, uint32_t *perm_out, void *stream);
+/* shm_route_bucket for shards cut at arbitrary boundaries.  splitters_host:
+ * HOST pointer to num_shards - 1 words, ascending (unsigned, not strictly);
+ * shard p owns [splitters[p - 1], splitters[p]), shard 0 from key 0 and the
+ * last shard up to 2^64, so a key's owner is the number of splitters <= it.
+ * A repeated splitter x makes an empty shard [x, x), and a key equal to x
+ * goes to the highest shard that starts at x.  The words are read during the
+ * call (they travel in the kernel arguments), not afterwards.  Counts, order
+ * inside a shard and perm as shm_route_bucket.  splitters_host == NULL behaves
+ * as shm_route_bucket, bit for bit (the same kernels).  SHM_EINVAL: a splitter
+ * below its predecessor, or one equal to kKeyMax (no key may be stored there),
+ * checked before the handle is used. */
+int shm_route_bucket_bounds(shm_tree *t, const uint64_t *keys, uint64_t n,
+                            uint32_t num_shards, const uint64_t *splitters_host,
+                            uint64_t *counts_out, uint64_t *keys_out,
+                            uint32_t *perm_out, void *stream);
 /* out[i] = in[perm[i]] (carry a companion array, e.g. insert values, along
  * with the bucketed keys). */
 int shm_route_permute(shm_tree *t, const uint64_t *in, const uint32_t *perm,
@@ -522,7 +554,8 @@ int shm_route_unpermute_found(shm_tree *t, const uint64_t *in, const uint32_t *p
 
 /* multi-GPU range shards over RCCL ------------------------------------------
  * Rank r of P (P <= 16) owns keys [r * 2^64 / P, (r+1) * 2^64 / P) in its own
- * shm_tree (create it with key_lo / key_bits of that slice).  One process per
+ * shm_tree (create it with key_lo / key_bits of that slice), until splitters
+ * are set (shm_shard_set_splitters, shm_shard_rebalance below).  One process per
  * GPU; every rank makes the same calls in the same order (collectives).
  * Every rank's tree has the same max_batch (checked at create).
  * A routed get: each key into its owner's run of fixed-size slots
@@ -602,6 +635,78 @@ int shm_shard_range_values(shm_shard *s, uint64_t *vals_out, uint64_t vals_cap, 
 /* Apply what a routed insert left for the next call (its overflow tails),
  * then shm_synchronize the local tree: the status of every routed batch. */
 int shm_shard_synchronize(shm_shard *s);
+
+/* Shards that follow the stored keys -----------------------------------------
+ * A shard handle starts with P equal slices of 2^64.  With splitters set,
+ * shard p owns [b[p], b[p + 1]) with b[0] = 0, b[P] = 2^64 and b[1 .. P - 1]
+ * the splitters, ascending and not strictly: a repeated splitter makes an
+ * empty shard, and a key's owner is the number of splitters <= it (as
+ * shm_route_bucket_bounds).  Routed gets, inserts, their overflow rounds and
+ * range scans all cut at the same boundaries; a shard with no splitters set
+ * runs the kernels it ran before they existed. */
+/* splitters_host: HOST pointer to P - 1 words; NULL = back to equal slices.
+ * A collective by convention: every rank passes the same words, checked with
+ * one exchange (as max_batch is at create); ranks that differ get SHM_EINVAL
+ * and keep their bounds.  Pending routed-insert tails are applied first (by
+ * the old bounds).  It MOVES NO DATA: pairs stored under the old bounds stay
+ * where they are, and a key whose owner changed is no longer found by routed
+ * calls until shm_shard_rebalance (or the caller) has moved it -- a caller who
+ * sets splitters over non-empty trees owns the consequences.  Meant for empty
+ * trees, e.g. a caller that sampled its first batch itself.  The local trees'
+ * key range hints are not changed (shm_tree_set_key_range).
+ * SHM_EINVAL: a null handle, descending splitters or one equal to kKeyMax,
+ * a shm_shard_search_begin ticket still outstanding, or ranks that disagree. */
+int shm_shard_set_splitters(shm_shard *s, const uint64_t *splitters_host);
+/* the current boundaries b[1 .. P - 1] (the equal slices' when none are set)
+ * into out_host (HOST, P - 1 words; may be NULL at P = 1); local, no exchange */
+int shm_shard_get_splitters(shm_shard *s, uint64_t *out_host);
+/* The even re-cut of P shards holding counts[p] pairs, by host arithmetic
+ * alone (no handle, no GPU, like shm_bulk_plan).  Shards are range-ordered,
+ * so the global sorted order is the shards' sorted contents in rank order:
+ * with N = sum(counts) and off[] its exclusive scan, old shard r holds global
+ * positions [off[r], off[r] + counts[r]).  New shard p holds [cut[p],
+ * cut[p + 1]) with cut[p] = floor(p N / P) (cut[P] = N), so new counts differ
+ * by at most 1.  send_cnt[p] = pairs `rank` sends to p (the overlap of its old
+ * positions with p's new ones), recv_cnt[p] = pairs it receives from p (the
+ * overlap of p's old positions with its new ones); a rank's own part is in
+ * both.  cut: P + 1 words, send_cnt / recv_cnt: P words each, all HOST.
+ * SHM_EINVAL: P = 0, P > 16, rank >= P or a null pointer. */
+int shm_rebalance_plan(const uint64_t *counts, uint32_t P, uint32_t rank,
+                       uint64_t *cut, uint64_t *send_cnt, uint64_t *recv_cnt);
+/* Rebalance: re-cut the stored pairs evenly over the shards and move them.
+ * Collective (every rank calls it with the same fills), exclusive and
+ * synchronising.  Per rank: pending routed-insert tails are applied; the
+ * whole local tree is exported in key order (shm_export's passes, as
+ * shm_compact) into a temporary device buffer of 16 B per pair; the ranks
+ * exchange their counts and each runs shm_rebalance_plan; new splitter j is
+ * the key at global position cut[j], contributed by the rank whose export
+ * holds it -- exact quantiles, no sampling and no global sort; each
+ * destination's contiguous run of the export (keys, then values) goes to it
+ * point to point, received in source-rank order, so the received run is
+ * already strictly ascending; the local tree's key range hint is set from the
+ * run (key_lo = its first key, key_bits = max(1, ceil(log2(last - first +
+ * 1))); a run of fewer than two pairs leaves the hint alone); the run is
+ * loaded with shm_bulk_load(leaf_fill, internal_fill) (0 / 0: 36 / 40), whose
+ * own input check runs on it as a cross-check; then the new bounds are
+ * installed.  *n_local_out (HOST, required) = this rank's new pair count.
+ * Afterwards every pair is where routed calls look for it, the counts differ
+ * by at most 1 across ranks, shm_stats' pages_used == shm_bulk_plan(n_local)
+ * .pages on every rank, and every consequence of a bulk load applies.  When
+ * fewer than P pairs are stored several cuts coincide: repeated splitters,
+ * empty shards.  When nothing is stored the bounds and the trees stay as they
+ * are.  At world 1 the call is a compaction.
+ * Temporary device memory per rank: 16 B x its old pairs + 16 B x its new
+ * pairs; the tree is rewritten in place.
+ * Checked by every rank before any tree is written, and agreed with one
+ * exchange: the fills, an outstanding shm_insert_order ticket on the local
+ * tree (SHM_EINVAL), shm_bulk_plan(n_new).pages + 1 against the arena's pages
+ * and the two temporary buffers (SHM_ENOMEM).  If any rank fails, every rank
+ * returns the status of the lowest such rank, and every tree, the bounds and
+ * the directories stay exactly as they were.  SHM_EINVAL without an exchange:
+ * a null handle or n_local_out, or a shm_shard_search_begin ticket still
+ * outstanding (every rank has it or none: collectives). */
+int shm_shard_rebalance(shm_shard *s, uint32_t leaf_fill, uint32_t internal_fill,
+                        uint64_t *n_local_out, void *stream);
 
 /* Tree::lock_bench (include/Tree.h:60, src/Tree.cpp:310-321) for a batch:
  * take and release lock[CityHash64(keys[i]) % num_locks] of the HBM lock

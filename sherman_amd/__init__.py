@@ -165,6 +165,7 @@ _SIGNATURES = [
     ("shm_index_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmIndexStats), ctypes.c_int]),
     ("shm_dir_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmDirStats)]),
     ("shm_route_bucket", ctypes.c_int, [vp, vp, u64, u32, vp, vp, vp, vp]),
+    ("shm_route_bucket_bounds", ctypes.c_int, [vp, vp, u64, u32, vp, vp, vp, vp, vp]),
     ("shm_route_permute", ctypes.c_int, [vp, vp, vp, u64, vp, vp]),
     ("shm_route_unpermute", ctypes.c_int, [vp, vp, vp, u64, vp, vp]),
     ("shm_route_unpermute_found", ctypes.c_int, [vp, vp, vp, u64, vp, vp, vp]),
@@ -183,6 +184,11 @@ _SIGNATURES = [
      [vp, vp, vp, u64, u64, vp, vp, vp, u64, u64, vp, vp]),
     ("shm_shard_synchronize", ctypes.c_int, [vp]),
     ("shm_shard_range_values", ctypes.c_int, [vp, vp, u64, vp]),
+    ("shm_tree_set_key_range", ctypes.c_int, [vp, u64, u32]),
+    ("shm_shard_set_splitters", ctypes.c_int, [vp, vp]),
+    ("shm_shard_get_splitters", ctypes.c_int, [vp, vp]),
+    ("shm_rebalance_plan", ctypes.c_int, [vp, u32, u32, vp, vp, vp]),
+    ("shm_shard_rebalance", ctypes.c_int, [vp, u32, u32, ctypes.POINTER(u64), vp]),
     ("shm_lock_bench", ctypes.c_int, [vp, vp, u64, vp]),
     ("shm_gen_keys", ctypes.c_int, [vp, u64, u64, u64, vp, vp]),
     ("shm_hash_keys", ctypes.c_int, [vp, vp, u64, u64, vp, vp]),
@@ -204,7 +210,11 @@ def lib():
                 "(there is no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
         for name, res, args in _SIGNATURES:
-            f = getattr(L, name)
+            f = getattr(L, name, None)
+            if f is None and os.environ.get("SHM_LIB_PATH"):
+                continue  # an older build under SHM_LIB_PATH (A/B of builds) lacks newer calls
+            if f is None:
+                raise ImportError(f"{LIB_PATH} lacks {name}: rebuild with `make -C sherman_amd`")
             f.restype = res
             f.argtypes = args
         if L.shm_abi_version() != ABI_VERSION:
@@ -228,6 +238,28 @@ def bulk_plan(n, leaf_fill=0, internal_fill=0):
     _check(lib().shm_bulk_plan(n, leaf_fill, internal_fill, ctypes.byref(p)), "bulk_plan")
     return {"pages": int(p.pages), "root_level": int(p.root_level),
             "level_pages": [int(x) for x in p.level_pages[:p.root_level + 1]]}
+
+
+def _host_u64(words):
+    """A ctypes array of u64 from Python ints / numpy u64 (None stays None)."""
+    if words is None:
+        return None
+    w = [int(x) & ((1 << 64) - 1) for x in words]
+    return (u64 * max(len(w), 1))(*w)
+
+
+def rebalance_plan(counts, rank):
+    """The even re-cut of len(counts) shards holding counts[p] pairs
+    (shm_rebalance_plan; host arithmetic, no GPU): {"cut": P + 1 global
+    positions, "send": pairs `rank` sends to each shard, "recv": pairs it
+    receives from each}.  P = 0, P > 16 or rank >= P raise
+    ShermanError(SHM_EINVAL)."""
+    P = len(counts)
+    c = _host_u64(counts)
+    cut, send, recv = (u64 * (P + 1))(), (u64 * max(P, 1))(), (u64 * max(P, 1))()
+    _check(lib().shm_rebalance_plan(c, P, rank, cut, send, recv), "rebalance_plan")
+    return {"cut": [int(x) for x in cut], "send": [int(x) for x in send[:P]],
+            "recv": [int(x) for x in recv[:P]]}
 
 
 def _ptr(x):
@@ -823,10 +855,30 @@ class Tree:
                "read_words")
         return list(buf)
 
-    def route_bucket(self, keys, num_shards, keys_out, perm_out, counts_out, stream=None):
-        _check(lib().shm_route_bucket(self.h, _ptr(keys), keys.numel(), num_shards,
-                                      _ptr(counts_out), _ptr(keys_out), _ptr(perm_out),
-                                      _stream_ptr(stream)), "route_bucket")
+    def route_bucket(self, keys, num_shards, keys_out, perm_out, counts_out, stream=None,
+                     splitters=None):
+        """Stable bucketing by owner.  splitters: num_shards - 1 ascending u64
+        boundaries (Python ints or numpy u64, host values; repeats make empty
+        shards), None: equal slices of 2^64."""
+        if splitters is None:
+            _check(lib().shm_route_bucket(self.h, _ptr(keys), keys.numel(), num_shards,
+                                          _ptr(counts_out), _ptr(keys_out), _ptr(perm_out),
+                                          _stream_ptr(stream)), "route_bucket")
+            return
+        if len(splitters) != num_shards - 1:
+            raise ValueError("route_bucket: num_shards - 1 splitters")
+        _check(lib().shm_route_bucket_bounds(self.h, _ptr(keys), keys.numel(), num_shards,
+                                             _host_u64(splitters), _ptr(counts_out),
+                                             _ptr(keys_out), _ptr(perm_out),
+                                             _stream_ptr(stream)), "route_bucket_bounds")
+
+    def set_key_range(self, key_lo, key_bits):
+        """Change the key range hint of the live tree (shm_tree_set_key_range):
+        exclusive and synchronising; the directory and the bucket table are
+        rebuilt over [key_lo, key_lo + 2^key_bits) by the next reader.  Keys
+        outside the hint are still stored and found."""
+        _check(lib().shm_tree_set_key_range(self.h, int(key_lo) & ((1 << 64) - 1), key_bits),
+               "set_key_range")
 
     def route_permute(self, vals_in, perm, out, stream=None):
         _check(lib().shm_route_permute(self.h, _ptr(vals_in), _ptr(perm), vals_in.numel(),
@@ -1032,6 +1084,30 @@ class CShard:
 
     def synchronize(self):
         _check(lib().shm_shard_synchronize(self.h), "shard_synchronize")
+
+    def set_splitters(self, splitters):
+        """The shards' boundaries b[1 .. P - 1] (shm_shard_set_splitters):
+        world - 1 ascending u64 values, the same on every rank (checked);
+        None: back to equal slices.  Moves no data."""
+        if splitters is not None and len(splitters) != self.world - 1:
+            raise ValueError("set_splitters: world - 1 splitters")
+        _check(lib().shm_shard_set_splitters(self.h, _host_u64(splitters)), "shard_set_splitters")
+
+    def splitters(self):
+        """The current boundaries b[1 .. P - 1] as Python ints (the equal
+        slices' when none are set)."""
+        out = (u64 * max(self.world - 1, 1))()
+        _check(lib().shm_shard_get_splitters(self.h, out), "shard_get_splitters")
+        return [int(x) for x in out[:self.world - 1]]
+
+    def rebalance(self, leaf_fill=0, internal_fill=0, stream=None):
+        """Re-cut the stored pairs evenly over the shards and move them
+        (shm_shard_rebalance; collective, exclusive, synchronising).  Returns
+        this rank's new pair count."""
+        n = u64(0)
+        _check(lib().shm_shard_rebalance(self.h, leaf_fill, internal_fill, ctypes.byref(n),
+                                         _stream_ptr(stream)), "shard_rebalance")
+        return int(n.value)
 
 
 def header_symbols(path=HEADER_PATH):

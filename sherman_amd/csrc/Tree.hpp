@@ -16,6 +16,7 @@
 //   (new) the tree of a sorted run, one pass    bulk_load(keys, vals, n[, leaf_fill, internal_fill])
 //   (new) every pair of a range, in key order   export_sorted(keys, vals, cap[, lo, hi]), count([lo, hi])
 //   (new) the tree rebuilt from its own pairs   compact([leaf_fill, internal_fill])
+//   (new) the key range hint of a live tree    set_key_range(key_lo, key_bits)
 //   (new) batched forms on device pointers      search_batch / insert_batch / mixed_batch
 //
 // The coroutine arguments are accepted and ignored, so call sites of the
@@ -218,6 +219,16 @@ class Tree {
     const int s = shm_compact(t_, leaf_fill, internal_fill, nullptr);
     if (s == SHM_EINVAL || s == SHM_ENOMEM) return false;
     check(s, "compact");
+    return true;
+  }
+
+  // Change the key range hint of the live tree (shm_tree_set_key_range): the
+  // next reader rebuilds the directory over [key_lo, key_lo + 2^key_bits).
+  // False: key_bits > 64 or an outstanding ordered chunk; other failures throw.
+  bool set_key_range(Key key_lo, uint32_t key_bits) {
+    const int s = shm_tree_set_key_range(t_, key_lo, key_bits);
+    if (s == SHM_EINVAL) return false;
+    check(s, "set_key_range");
     return true;
   }
 

@@ -526,13 +526,25 @@ void launch_gen_keys(uint64_t first, uint64_t n, uint64_t keyspace,
                      uint64_t* out, hipStream_t s);
 void launch_hash_ids(const uint64_t* ids, uint64_t n, uint64_t keyspace, uint64_t* out,
                      hipStream_t s);
+// The shards' boundaries for routing: s[j - 1] = the first key of shard j
+// (j = 1 .. P - 1, ascending, repeats allowed: shard [x, x) is empty, none
+// equals kKeyMax), so a key's owner is the number of splitters <= it.  Passed
+// by value in the kernel arguments.  Every routing launch takes a nullable
+// split (nullptr: equal slices, the kernels as they were before splitters)
+// and a mode for the owner search (0 or 2: binary search in LDS; 1: compare-
+// and-add over the kernel arguments, P <= 16, measured slower --
+// tools/route_bounds.py)
+struct RouteSplit {
+  uint64_t s[63];
+};
 // stable bucketing by owning shard; cm = route_scratch_words(n) words
 uint64_t route_scratch_words(uint64_t n_max);
 // keymax / err (nullable): a routed insert's batch holding kKeyMax is
 // rejected whole (every count 0, kErrKeyMax in *err; keymax: a zeroed word)
 void launch_route_bucket(const uint64_t* keys, uint64_t n, uint32_t shards,
                          uint64_t* counts, uint64_t* keys_out, uint32_t* perm,
-                         uint32_t* cm, uint32_t* keymax, uint32_t* err, hipStream_t s);
+                         uint32_t* cm, uint32_t* keymax, uint32_t* err, hipStream_t s,
+                         const RouteSplit* split = nullptr, int mode = 0);
 // out[i] = in[perm[i]]
 void launch_permute(const uint64_t* in, const uint32_t* perm, uint64_t n, uint64_t* out,
                     hipStream_t s);
@@ -555,7 +567,8 @@ inline uint64_t route_ctr_words(uint32_t P) { return (uint64_t)(P + 2) * kCtrStr
 void launch_route_slots(const uint64_t* keys, uint64_t n, uint32_t P, uint64_t cap,
                         uint32_t* cursor, uint32_t* ctr, uint64_t* out, uint32_t* spos,
                         uint64_t* ovk, uint32_t* ovi, uint32_t* err, hipStream_t s, uint32_t own = 0,
-                        uint64_t* own_out = nullptr, bool fill = true);
+                        uint64_t* own_out = nullptr, bool fill = true,
+                        const RouteSplit* split = nullptr, int mode = 0);
 // out[i] = in[spos[i]]; with own_src non-null, slots of run `own` (own * cap
 // .. + cap) are read from own_src (the local get's results, never exchanged)
 void launch_route_gather(const uint64_t* in, const uint32_t* spos, uint64_t n, uint64_t* out,
@@ -571,7 +584,8 @@ void launch_route_ov_scatter(const uint64_t* in, const uint32_t* perm, const uin
 void launch_route_pack(const uint64_t* kb, const uint64_t* vb, const uint64_t* cnt, uint32_t P,
                        uint64_t cap, uint64_t* pk, uint64_t* pv, hipStream_t s, uint32_t own = 0,
                        uint64_t* own_k = nullptr, uint64_t* own_v = nullptr);
-// routed range scans: shard p owns [b[p], b[p + 1]) (P <= 16; b[P] unused)
+// routed range scans: shard p owns [b[p], b[p + 1]) (P <= 16; b[P] unused);
+// b[p + 1] <= b[p] (repeated splitters): shard p owns nothing
 struct ShardBounds {
   uint64_t b[17];
 };

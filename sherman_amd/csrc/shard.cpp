@@ -49,6 +49,11 @@
 //            pieces' values in shard order = key order (Tree::range_query,
 //            Tree.cpp:461-540, intended semantics).
 //
+// The shards start as equal slices; shm_shard_set_splitters and
+// shm_shard_rebalance replace them with boundaries that follow the stored
+// keys (shard p owns [b[p], b[p + 1]), an owner = the number of splitters <=
+// the key), and every route above then cuts at those.
+//
 // A search is split in two calls so a caller can pipeline batches: begin
 // (placement + key exchange) and end (the rest).  Each of the handle's two
 // search slots has its own buffers and its own communicator (split from the
@@ -79,8 +84,10 @@ extern "C" uint32_t* shm__error_word(shm_tree* t);
 extern "C" int shm__insert_batch_padded(shm_tree* t, const uint64_t* keys, const uint64_t* vals,
                                         uint64_t n, void* stream);
 extern "C" int shm__route_bucket_insert(shm_tree* t, const uint64_t* keys, uint64_t n,
-                                        uint32_t num_shards, uint64_t* counts_out,
-                                        uint64_t* keys_out, uint32_t* perm_out, void* stream);
+                                        uint32_t num_shards, const uint64_t* splitters_host,
+                                        uint64_t* counts_out, uint64_t* keys_out,
+                                        uint32_t* perm_out, void* stream);
+extern "C" int shm__export_all(shm_tree* t, uint64_t** pairs_out, uint64_t* n_out, void* stream);
 extern "C" int shm__scan_u64(shm_tree* t, const uint64_t* in, uint64_t* out, uint64_t n,
                              uint64_t* tot_dev, void* stream);
 
@@ -428,6 +435,13 @@ struct shm_shard {
   ExclCtx ex;
   hipStream_t side = nullptr;     // read-backs that wait on an event
   shm::dev::ShardBounds bnd{};
+  // shm_shard_set_splitters / shm_shard_rebalance: the boundaries b[1 .. P - 1]
+  // as the routing kernels take them; unset: equal slices (the kernels and
+  // bnd as they were before splitters)
+  bool has_split = false;
+  shm::dev::RouteSplit split{};
+  const shm::dev::RouteSplit* route_split() const { return has_split ? &split : nullptr; }
+  const uint64_t* host_split() const { return has_split ? split.s : nullptr; }
   // shm__shard_force_route: even at world 1 every get and insert takes the
   // routed path -- slot placement, the exchange through the transport (each
   // rank's own run included, so RCCL sends it to itself), the local batch,
@@ -453,6 +467,22 @@ void free_shard(shm_shard* h) {
   // xp[0] may own the base communicator: destroy the splits first
   for (int i = 2; i >= 0; --i) delete h->xp[i];
   delete h;
+}
+
+// shard p owns [ceil(p 2^64 / P), ceil((p + 1) 2^64 / P))
+void equal_bounds(shm_shard* h) {
+  const uint32_t P = h->world;
+  h->has_split = false;
+  h->split = shm::dev::RouteSplit{};
+  for (uint32_t p = 0; p < P; ++p)
+    h->bnd.b[p] = (uint64_t)((((unsigned __int128)p << 64) + P - 1) / P);
+}
+// shard p owns [sp[p - 1], sp[p]) (sp: P - 1 ascending words; b[0] = 0)
+void split_bounds(shm_shard* h, const uint64_t* sp) {
+  h->has_split = true;
+  h->split = shm::dev::RouteSplit{};
+  h->bnd.b[0] = 0;
+  for (uint32_t p = 1; p < h->world; ++p) h->bnd.b[p] = h->split.s[p - 1] = sp[p - 1];
 }
 
 int alloc_shard(shm_shard* h) {
@@ -492,9 +522,7 @@ int alloc_shard(shm_shard* h) {
   rc |= dalloc(&e.rw, 2 * (uint64_t)P + 8);
   if (hipEventCreateWithFlags(&e.ev_ins, hipEventDisableTiming) != hipSuccess) rc |= SHM_EIO;
   if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) rc |= SHM_EIO;
-  // shard p owns [ceil(p 2^64 / P), ceil((p + 1) 2^64 / P))
-  for (uint32_t p = 0; p < P; ++p)
-    h->bnd.b[p] = (uint64_t)((((unsigned __int128)p << 64) + P - 1) / P);
+  equal_bounds(h);
   return rc ? SHM_ENOMEM : SHM_OK;
 }
 
@@ -628,7 +656,9 @@ int get_overflow(shm_shard* h, GetSlot& s, uint64_t* vals_out, uint8_t* found_ou
   hipStream_t st = s.stream;
   // the cut keys grouped by owner (stable), exchanged exactly, searched, and
   // their values sent back and scattered to the inputs they came from
-  if (m) RC_OK(shm_route_bucket(h->local, s.ovk, m, P, s.ocnt, s.okb, s.operm, st));
+  if (m)
+    RC_OK(shm_route_bucket_bounds(h->local, s.ovk, m, P, h->host_split(), s.ocnt, s.okb, s.operm,
+                                  st));
   RC_OK(ensure(s.ork, s.orcap, mr, st));
   RC_OK(ensure(s.orv, s.orvcap, mr, st));
   RC_OK(s.x->p2p(s.okb, scnt.data(), soff.data(), s.ork, rcnt.data(), roff.data(), 8, st));
@@ -724,7 +754,8 @@ int shm_shard_search_begin(shm_shard* h, const uint64_t* keys, uint64_t n, void*
   s.filled = s.ncap;
   shm::dev::launch_route_slots(s.keys, s.n, P, s.ncap, s.cw, s.ctr, s.pk, s.spos, s.ovk, s.ovi,
                                shm__error_word(h->local), s.stream, me,
-                               h->force_route ? nullptr : s.pr + (uint64_t)me * s.ncap, fill);
+                               h->force_route ? nullptr : s.pr + (uint64_t)me * s.ncap, fill,
+                               h->route_split());
   HIP_OK2(hipGetLastError());
   RC_OK(s.x->group_start());
   RC_OK(s.x->a2a_peers(s.pk, s.pr, s.ncap, 8, s.stream));
@@ -770,7 +801,7 @@ int shm_shard_insert(shm_shard* h, const uint64_t* keys, const uint64_t* vals, u
   const uint32_t P = h->world;
   // a batch holding kKeyMax routes nothing (SHM_EINVAL at the next
   // synchronising call), as a local insert rejects its chunk
-  RC_OK(shm__route_bucket_insert(h->local, keys, n, P, e.icnt, e.kb, e.perm, s));
+  RC_OK(shm__route_bucket_insert(h->local, keys, n, P, h->host_split(), e.icnt, e.kb, e.perm, s));
   RC_OK(shm_route_permute(h->local, vals, e.perm, n, e.vb, s));
   // this rank's own run is packed straight into its receive slot (forced:
   // it crosses the transport like the peers')
@@ -924,6 +955,211 @@ int shm_shard_range_values(shm_shard* h, uint64_t* vals_out, uint64_t vals_cap, 
   return hipGetLastError() == hipSuccess ? SHM_OK : SHM_EIO;
 }
 
+}  // extern "C"
+
+namespace {
+// P - 1 host words: ascending (repeats allowed), none kKeyMax
+bool splitters_ok(const uint64_t* sp, uint32_t P) {
+  for (uint32_t j = 0; j + 1 < P; ++j)
+    if (sp[j] == ~0ull || (j && sp[j] < sp[j - 1])) return false;
+  return true;
+}
+
+// `per` words of this rank to every rank and theirs back, through the
+// exclusive calls' transport on stream s, with a host wait: send = P runs of
+// per words (run p for rank p), recv likewise (run q from rank q).  d: 2 * P *
+// per device words.
+int exchange_words(shm_shard* h, uint64_t* d, const std::vector<uint64_t>& send,
+                   std::vector<uint64_t>& recv, uint32_t per, hipStream_t s) {
+  const uint64_t w = (uint64_t)h->world * per;
+  recv.assign(w, 0);
+  HIP_OK2(hipMemcpyAsync(d, send.data(), 8 * w, hipMemcpyHostToDevice, s));
+  RC_OK(h->ex.x->a2a(d, d + w, per, 8, s));
+  HIP_OK2(hipMemcpyAsync(recv.data(), d + w, 8 * w, hipMemcpyDeviceToHost, s));
+  HIP_OK2(hipStreamSynchronize(s));
+  return SHM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int shm_shard_set_splitters(shm_shard* h, const uint64_t* splitters_host) {
+  if (!h) return SHM_EINVAL;
+  const uint32_t P = h->world;
+  if (splitters_host && !splitters_ok(splitters_host, P)) return SHM_EINVAL;
+  if (h->slot[0].busy || h->slot[1].busy) return SHM_EINVAL;  // a begun get was placed by the old bounds
+  RC_OK(flush(h));
+  // every rank passes the same words: one exchange of {set, the P - 1 words}
+  std::vector<uint64_t> mine(P, 0), send((uint64_t)P * P), recv;
+  mine[0] = splitters_host ? 1 : 0;
+  for (uint32_t j = 0; splitters_host && j + 1 < P; ++j) mine[1 + j] = splitters_host[j];
+  for (uint32_t p = 0; p < P; ++p) std::copy(mine.begin(), mine.end(), send.begin() + (uint64_t)p * P);
+  uint64_t* d = nullptr;
+  if (dalloc(&d, 2ull * P * P)) return SHM_ENOMEM;
+  const int rc = exchange_words(h, d, send, recv, P, h->side);
+  dfree(d);
+  RC_OK(rc);
+  for (uint32_t q = 0; q < P; ++q)
+    if (!std::equal(mine.begin(), mine.end(), recv.begin() + (uint64_t)q * P)) {
+      fprintf(stderr, "sherman_amd: rank %u and rank %u passed different splitters\n", h->rank, q);
+      return SHM_EINVAL;
+    }
+  if (splitters_host)
+    split_bounds(h, splitters_host);
+  else
+    equal_bounds(h);
+  h->ex.last_ok = false;
+  return SHM_OK;
+}
+
+int shm_shard_get_splitters(shm_shard* h, uint64_t* out_host) {
+  if (!h || (h->world > 1 && !out_host)) return SHM_EINVAL;
+  for (uint32_t p = 1; p < h->world; ++p) out_host[p - 1] = h->bnd.b[p];
+  return SHM_OK;
+}
+
+int shm_rebalance_plan(const uint64_t* counts, uint32_t P, uint32_t rank, uint64_t* cut,
+                       uint64_t* send_cnt, uint64_t* recv_cnt) {
+  if (!counts || !cut || !send_cnt || !recv_cnt || P == 0 || P > kMaxWorld || rank >= P)
+    return SHM_EINVAL;
+  uint64_t off[kMaxWorld + 1];
+  off[0] = 0;
+  for (uint32_t p = 0; p < P; ++p) off[p + 1] = off[p] + counts[p];
+  const uint64_t N = off[P];
+  for (uint32_t p = 0; p <= P; ++p) cut[p] = (uint64_t)(((unsigned __int128)N * p) / P);
+  auto overlap = [](uint64_t a0, uint64_t a1, uint64_t b0, uint64_t b1) -> uint64_t {
+    const uint64_t lo = std::max(a0, b0), hi = std::min(a1, b1);
+    return hi > lo ? hi - lo : 0;
+  };
+  for (uint32_t p = 0; p < P; ++p) {
+    send_cnt[p] = overlap(off[rank], off[rank + 1], cut[p], cut[p + 1]);
+    recv_cnt[p] = overlap(off[p], off[p + 1], cut[rank], cut[rank + 1]);
+  }
+  return SHM_OK;
+}
+
+int shm_shard_rebalance(shm_shard* h, uint32_t leaf_fill, uint32_t internal_fill,
+                        uint64_t* n_local_out, void* stream) {
+  if (!h || !n_local_out) return SHM_EINVAL;
+  if (h->slot[0].busy || h->slot[1].busy) return SHM_EINVAL;
+  RC_OK(flush(h));
+  const uint32_t P = h->world, me = h->rank;
+  hipStream_t s = (hipStream_t)stream;
+  ExclCtx& e = h->ex;
+  e.last_ok = false;
+  // From here on a rank that fails keeps taking part until the ranks have
+  // agreed (st travels with the counts and again with the splitters): no rank
+  // writes its tree unless every rank can.
+  shm_bulk_plan_t pl{};
+  int st = shm_bulk_plan(0, leaf_fill, internal_fill, &pl);
+  uint64_t* pairs = nullptr;  // the old pairs: keys [0, n_old), values [n_old, 2 n_old)
+  uint64_t n_old = 0;
+  if (!st) st = shm__export_all(h->local, &pairs, &n_old, s);
+  uint64_t *d = nullptr, *rk = nullptr;
+  auto done = [&](int rc) {
+    dfree(d);
+    dfree(rk);
+    dfree(pairs);
+    return rc;
+  };
+  if (dalloc(&d, 2ull * P * (P + 1))) return done(SHM_ENOMEM);
+  auto first_bad = [&](const std::vector<uint64_t>& r, uint32_t per) {
+    for (uint32_t q = 0; q < P; ++q)
+      if (r[(uint64_t)q * per + per - 1]) return (int)(int64_t)r[(uint64_t)q * per + per - 1];
+    return SHM_OK;
+  };
+  // the counts (an all-gather: the same {count, status} to every rank)
+  std::vector<uint64_t> send(2ull * P), recv;
+  for (uint32_t p = 0; p < P; ++p) {
+    send[2 * p] = n_old;
+    send[2 * p + 1] = (uint64_t)(int64_t)st;
+  }
+  if (const int rc = exchange_words(h, d, send, recv, 2, s)) return done(rc);
+  if (const int bad = first_bad(recv, 2)) return done(bad);
+  std::vector<uint64_t> counts(P), cut(P + 1), scnt(P), rcnt(P), soff(P), roff(P);
+  for (uint32_t p = 0; p < P; ++p) counts[p] = recv[2 * p];
+  if (const int rc = shm_rebalance_plan(counts.data(), P, me, cut.data(), scnt.data(), rcnt.data()))
+    return done(rc);
+  const uint64_t N = cut[P], n_new = cut[me + 1] - cut[me];
+  if (N == 0) {  // nothing stored anywhere: the bounds and the trees stay
+    *n_local_out = 0;
+    return done(SHM_OK);
+  }
+  // everything that can fail, before any tree is written
+  st = shm_bulk_plan(n_new, leaf_fill, internal_fill, &pl);
+  shm_stats_t stats{};
+  if (!st) st = shm_stats(h->local, &stats);
+  // as shm_bulk_load: the plan's pages and the superblock (pages_capacity
+  // leaves the superblock out)
+  if (!st && pl.pages > stats.pages_capacity) st = SHM_ENOMEM;
+  if (!st && n_new && dalloc(&rk, 2 * n_new)) {
+    (void)hipGetLastError();
+    st = SHM_ENOMEM;
+  }
+  // splitter j = the key at global position cut[j]: the rank holding that
+  // position reads it from its export, the others contribute 0
+  uint64_t my_off = 0;
+  for (uint32_t p = 0; p < me; ++p) my_off += counts[p];
+  std::vector<uint64_t> mine(P + 1, 0);
+  for (uint32_t j = 1; j < P; ++j)
+    if (cut[j] >= my_off && cut[j] - my_off < n_old &&
+        hipMemcpyAsync(&mine[j - 1], pairs + (cut[j] - my_off), 8, hipMemcpyDeviceToHost, s) !=
+            hipSuccess)
+      st = st ? st : SHM_EIO;
+  if (hipStreamSynchronize(s) != hipSuccess) st = st ? st : SHM_EIO;
+  mine[P] = (uint64_t)(int64_t)st;
+  send.assign((uint64_t)P * (P + 1), 0);
+  for (uint32_t p = 0; p < P; ++p)
+    std::copy(mine.begin(), mine.end(), send.begin() + (uint64_t)p * (P + 1));
+  if (const int rc = exchange_words(h, d, send, recv, P + 1, s)) return done(rc);
+  if (const int bad = first_bad(recv, P + 1)) return done(bad);
+  uint64_t sp[kMaxWorld] = {};
+  for (uint32_t j = 1; j < P; ++j)
+    for (uint32_t q = 0; q < P; ++q) sp[j - 1] = std::max(sp[j - 1], recv[(uint64_t)q * (P + 1) + j - 1]);
+  if (!splitters_ok(sp, P)) return done(SHM_EIO);  // the exports were not one ascending run
+  // the move: destination p's contiguous run of the export, keys then values;
+  // the receive buffer fills in source-rank order, so it ascends
+  uint64_t so = 0, ro = 0;
+  for (uint32_t p = 0; p < P; ++p) {
+    soff[p] = so;
+    so += scnt[p];
+    roff[p] = ro;
+    ro += rcnt[p];
+  }
+  if (so != n_old || ro != n_new || scnt[me] != rcnt[me]) return done(SHM_EIO);
+  int rc = SHM_OK;
+  // this rank's own part never enters the transport
+  if (scnt[me] &&
+      (hipMemcpyAsync(rk + roff[me], pairs + soff[me], 8 * scnt[me], hipMemcpyDeviceToDevice, s) !=
+           hipSuccess ||
+       hipMemcpyAsync(rk + n_new + roff[me], pairs + n_old + soff[me], 8 * scnt[me],
+                      hipMemcpyDeviceToDevice, s) != hipSuccess))
+    rc = SHM_EIO;
+  scnt[me] = rcnt[me] = 0;
+  if (!rc) rc = e.x->group_start();
+  if (!rc) rc = e.x->p2p(pairs, scnt.data(), soff.data(), rk, rcnt.data(), roff.data(), 8, s);
+  if (!rc)
+    rc = e.x->p2p(pairs ? pairs + n_old : nullptr, scnt.data(), soff.data(), rk ? rk + n_new : nullptr,
+                  rcnt.data(), roff.data(), 8, s);
+  if (!rc) rc = e.x->group_end();
+  if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = SHM_EIO;
+  // the hint from the run: [first, first + 2^bits) holds every key of it
+  if (!rc && n_new >= 2) {
+    uint64_t fl[2] = {0, 0};
+    if (hipMemcpy(&fl[0], rk, 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&fl[1], rk + n_new - 1, 8, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = SHM_EIO;
+    const uint64_t span1 = fl[1] - fl[0];  // span - 1 >= 1 for an ascending run
+    const uint32_t bits = std::max(1, 64 - __builtin_clzll(span1 | 1));
+    if (!rc && fl[1] > fl[0]) rc = shm_tree_set_key_range(h->local, fl[0], bits);
+  }
+  if (!rc) rc = shm_bulk_load(h->local, rk, rk ? rk + n_new : nullptr, n_new, leaf_fill, internal_fill, s);
+  if (rc) return done(rc);
+  split_bounds(h, sp);
+  *n_local_out = n_new;
+  return done(SHM_OK);
+}
+
 // Library-internal test hooks, not part of include/sherman_amd.h.
 // (1) The routed get's slot placement and result gather for P shards, so the
 // placement can be checked on one GPU without P ranks (tests/test_gpu_shard.py).
@@ -965,6 +1201,24 @@ int shm__route_slots_ex(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t 
   if (!ctr) return SHM_ENOMEM;
   shm::dev::launch_route_slots(keys, n, P, cap, cursor, ctr, slots, spos, ovk, ovi,
                                shm__error_word(t), (hipStream_t)stream, 0, nullptr, fill != 0);
+  return hipGetLastError() == hipSuccess ? SHM_OK : SHM_EIO;
+}
+// ... and with splitters (host words, nullable) and the owner search named
+// (kernels.h RouteSplit: 0 or 2 LDS, 1 kernel arguments)
+int shm__route_slots_bounds(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t P, uint64_t cap,
+                            uint32_t* cursor, uint64_t* slots, uint32_t* spos, uint64_t* ovk,
+                            uint32_t* ovi, int fill, const uint64_t* splitters_host, int mode,
+                            void* stream) {
+  if (!t || !cursor || !slots || !spos || P == 0 || P > 64 || (n && !keys) ||
+      (uint64_t)P * cap >= ~0u || (splitters_host && !splitters_ok(splitters_host, P)))
+    return SHM_EINVAL;
+  uint32_t* ctr = hook_ctr();
+  if (!ctr) return SHM_ENOMEM;
+  shm::dev::RouteSplit sp{};
+  for (uint32_t j = 0; splitters_host && j + 1 < P; ++j) sp.s[j] = splitters_host[j];
+  shm::dev::launch_route_slots(keys, n, P, cap, cursor, ctr, slots, spos, ovk, ovi,
+                               shm__error_word(t), (hipStream_t)stream, 0, nullptr, fill != 0,
+                               splitters_host ? &sp : nullptr, mode);
   return hipGetLastError() == hipSuccess ? SHM_OK : SHM_EIO;
 }
 int shm__route_gather(const uint64_t* in, const uint32_t* spos, uint64_t n, uint64_t* vals_out,

@@ -2703,6 +2703,64 @@ int shm_compact(shm_tree* t, uint32_t leaf_fill, uint32_t internal_fill, void* s
   return rc;
 }
 
+// Library-internal (shard.cpp shm_shard_rebalance): the whole tree exported
+// into a fresh device buffer the caller frees with hipFree, keys in
+// (*pairs_out)[0, n), values in [n, 2 n) (nullptr for n == 0), as shm_compact
+// takes it.  Read-only.  SHM_EINVAL with an outstanding shm_insert_order
+// ticket: the load that follows would refuse it.
+int shm__export_all(shm_tree* t, uint64_t** pairs_out, uint64_t* n_out, void* stream) {
+  if (!t || !pairs_out || !n_out) return SHM_EINVAL;
+  *pairs_out = nullptr;
+  *n_out = 0;
+  std::lock_guard<std::mutex> g(t->mu);
+  if (t->n_pend) return SHM_EINVAL;
+  hipStream_t s = pick(stream);
+  Order ord(t, s, true);
+  if (ord.rc) return ord.rc;
+  uint64_t n = 0;
+  if (const int rc = export_count(t, s, 0, kKeyMax, &n)) return rc;
+  uint64_t* pairs = nullptr;
+  if (n && dalloc(&pairs, 2 * n)) {
+    (void)hipGetLastError();
+    const int e = check_err(t, s);
+    return e ? e : SHM_ENOMEM;
+  }
+  const int rc = export_write(t, s, 0, kKeyMax, pairs, pairs ? pairs + n : nullptr, n);
+  if (rc) {
+    if (pairs) (void)hipFree(pairs);
+    return rc;
+  }
+  *pairs_out = pairs;
+  *n_out = n;
+  return SHM_OK;
+}
+
+int shm_tree_set_key_range(shm_tree* t, uint64_t key_lo, uint32_t key_bits) {
+  // the arguments first: a rejected call uses neither the handle nor the GPU
+  if (key_bits > 64 || !t) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  if (t->n_pend) return SHM_EINVAL;  // an ordered chunk was partitioned by the old range
+  // exclusive and synchronising, as shm_bulk_load: every launch that took the
+  // old range in its arguments (gets, the chunks' directory and table upkeep)
+  // has run before the range changes
+  HIP_OK(hipDeviceSynchronize());
+  mirror(t);
+  if (const int rc = dir_poll(t, true)) return rc;
+  if (const int rc = vt_poll(t, true)) return rc;
+  t->cfg.key_bits = key_bits ? key_bits : 64;
+  t->cfg.key_lo = t->cfg.key_bits == 64 ? 0 : key_lo;
+  // what the old range laid out, as shm_bulk_load drops it: the next reader
+  // builds the directory (its entry count from the new key_bits: dir_bits_for),
+  // the level hints and the bucket table over the new range
+  t->dir_valid = false;
+  t->hint_ok = false;
+  t->top_valid = false;
+  t->vt_valid = false;
+  // the table was dropped at this size because of the old range's dead buckets
+  t->vt_drop_bits = 0;
+  return SHM_OK;
+}
+
 int shm_check(shm_tree* t, uint64_t* n_leaves, uint64_t* n_internal,
               uint64_t* n_keys) {
   if (!t) return SHM_EINVAL;
@@ -2918,35 +2976,62 @@ int shm_profile_read(shm_tree* t, shm_profile_t* out, int reset) {
 
 namespace {
 int route_bucket(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
-                 uint64_t* counts_out, uint64_t* keys_out, uint32_t* perm_out, void* stream,
-                 bool reject_keymax);
+                 const uint64_t* splitters, uint64_t* counts_out, uint64_t* keys_out,
+                 uint32_t* perm_out, void* stream, bool reject_keymax, int mode = 0);
 }
 
 int shm_route_bucket(shm_tree* t, const uint64_t* keys, uint64_t n,
                      uint32_t num_shards, uint64_t* counts_out,
                      uint64_t* keys_out, uint32_t* perm_out, void* stream) {
-  return route_bucket(t, keys, n, num_shards, counts_out, keys_out, perm_out, stream, false);
+  return route_bucket(t, keys, n, num_shards, nullptr, counts_out, keys_out, perm_out, stream,
+                      false);
+}
+
+int shm_route_bucket_bounds(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
+                            const uint64_t* splitters_host, uint64_t* counts_out,
+                            uint64_t* keys_out, uint32_t* perm_out, void* stream) {
+  return route_bucket(t, keys, n, num_shards, splitters_host, counts_out, keys_out, perm_out,
+                      stream, false);
 }
 
 // Library-internal (shard.cpp shm_shard_insert): the bucketing of a routed
 // insert; a batch holding kKeyMax is rejected whole on the sending rank
 // (nothing routed, SHM_EINVAL at the next synchronising call), as a local
 // insert rejects its chunk (the receivers skip kKeyMax as slot
-// padding, so it must be caught before packing)
+// padding, so it must be caught before packing).  splitters_host: nullable,
+// as shm_route_bucket_bounds
 int shm__route_bucket_insert(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
-                             uint64_t* counts_out, uint64_t* keys_out, uint32_t* perm_out,
-                             void* stream) {
-  return route_bucket(t, keys, n, num_shards, counts_out, keys_out, perm_out, stream, true);
+                             const uint64_t* splitters_host, uint64_t* counts_out,
+                             uint64_t* keys_out, uint32_t* perm_out, void* stream) {
+  return route_bucket(t, keys, n, num_shards, splitters_host, counts_out, keys_out, perm_out,
+                      stream, true);
+}
+
+// Library-internal (tools/route_bounds.py, tests): shm_route_bucket_bounds with
+// the owner search named (kernels.h RouteSplit: 0 or 2 LDS, 1 kernel arguments)
+int shm__route_bucket_mode(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
+                           const uint64_t* splitters_host, int mode, uint64_t* counts_out,
+                           uint64_t* keys_out, uint32_t* perm_out, void* stream) {
+  return route_bucket(t, keys, n, num_shards, splitters_host, counts_out, keys_out, perm_out,
+                      stream, false, mode);
 }
 
 }  // extern "C"
 
 namespace {
 int route_bucket(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
-                 uint64_t* counts_out, uint64_t* keys_out, uint32_t* perm_out, void* stream,
-                 bool reject_keymax) {
+                 const uint64_t* splitters, uint64_t* counts_out, uint64_t* keys_out,
+                 uint32_t* perm_out, void* stream, bool reject_keymax, int mode) {
   if (!t || num_shards == 0 || num_shards > 64 || !counts_out) return SHM_EINVAL;
   if (n && (!keys || !keys_out || !perm_out)) return SHM_EINVAL;
+  // ascending (repeats make empty shards), none kKeyMax: checked on the host
+  // words before the handle is used
+  dev::RouteSplit sp{};
+  if (splitters)
+    for (uint32_t j = 0; j + 1 < num_shards; ++j) {
+      if (splitters[j] == kKeyMax || (j && splitters[j] < splitters[j - 1])) return SHM_EINVAL;
+      sp.s[j] = splitters[j];
+    }
   if (n > t->nmax) return SHM_E2BIG;
   std::lock_guard<std::mutex> g(t->mu);
   hipStream_t s = pick(stream);
@@ -2965,7 +3050,8 @@ int route_bucket(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_sha
   }
   // d_err[3]: the kKeyMax flag of a routed insert (zero between calls)
   dev::launch_route_bucket(keys, n, num_shards, counts_out, keys_out, perm_out, scratch,
-                           reject_keymax ? t->d_err + 3 : nullptr, t->d_err, s);
+                           reject_keymax ? t->d_err + 3 : nullptr, t->d_err, s,
+                           splitters ? &sp : nullptr, mode);
   HIP_OK(hipGetLastError());
   return SHM_OK;
 }

@@ -199,13 +199,66 @@ void launch_hash_ids(const uint64_t* ids, uint64_t n, uint64_t keyspace, uint64_
   if (n) hipLaunchKernelGGL(k_hash_ids, grid1(n), dim3(kT), 0, s, ids, n, keyspace, out);
 }
 
-// ---- multi-GPU routing: shard s owns [s*2^64/P, (s+1)*2^64/P) -------------
+// ---- multi-GPU routing -------------------------------------------------------
+// Equal slices (no splitters): shard s owns [s*2^64/P, (s+1)*2^64/P).
 __device__ __forceinline__ uint32_t owner_of(uint64_t k, uint32_t shards) {
   return (uint32_t)__umul64hi(k, (uint64_t)shards);
 }
 constexpr int kRouteMaxShards = 64;
 constexpr int kRoutePer = 4;  // keys per thread
 constexpr int kRouteTile = kT * kRoutePer;
+
+// Splitters (RouteSplit, kernels.h): shard p owns [s[p - 1], s[p]), so a key's
+// owner is the number of splitters <= it.  The routing kernels are templates
+// on how they find it; kOwnSlices is the code they were before splitters:
+//   kOwnSlices : __umul64hi, no splitters anywhere
+//   kOwnArgs   : P <= kRouteArgShards: compare-and-add over the splitters in
+//                the kernel arguments (wave-uniform scalar loads, no LDS);
+//                measured slower, kept selectable (own_mode)
+//   kOwnLds    : the splitters copied to LDS once per block (padded with
+//                kKeyMax to 64 words), a branchless binary search of
+//                ceil(log2 P) steps: what every splitter launch uses
+constexpr int kOwnSlices = 0, kOwnArgs = 1, kOwnLds = 2;
+constexpr uint32_t kRouteArgShards = 16;
+
+template <int M>
+__device__ __forceinline__ uint64_t* split_lds() {
+  if constexpr (M == kOwnLds) {
+    __shared__ uint64_t s_split[kRouteMaxShards];
+    return s_split;
+  } else {
+    return nullptr;
+  }
+}
+// before the block's first __syncthreads (every routing kernel has one ahead
+// of its first owner)
+template <int M>
+__device__ __forceinline__ void split_stage(uint64_t* lds, const RouteSplit& sp, uint32_t P) {
+  if constexpr (M == kOwnLds) {
+    if (threadIdx.x < (uint32_t)kRouteMaxShards)
+      lds[threadIdx.x] = threadIdx.x + 1 < P ? sp.s[threadIdx.x] : kKeyMax;
+  }
+}
+template <int M>
+__device__ __forceinline__ uint32_t owner_by(uint64_t k, uint32_t P, const RouteSplit& sp,
+                                             const uint64_t* lds) {
+  if constexpr (M == kOwnSlices) {
+    return owner_of(k, P);
+  } else if constexpr (M == kOwnArgs) {
+    uint32_t o = 0;
+#pragma unroll
+    for (uint32_t j = 0; j + 1 < kRouteArgShards; ++j) o += (j + 1 < P && sp.s[j] <= k) ? 1u : 0u;
+    return o;
+  } else {
+    // the count of words <= k among the 2^nb - 1 first ones (ascending; the
+    // padding counts only for k == kKeyMax, cut below)
+    const int nb = P > 1 ? 32 - __clz((int)(P - 1)) : 0;
+    uint32_t o = 0;
+    for (uint32_t step = nb ? 1u << (nb - 1) : 0u; step; step >>= 1)
+      o += lds[o + step - 1] <= k ? step : 0u;
+    return o < P - 1 ? o : P - 1;
+  }
+}
 
 // Stable bucketing by owner (keys_out keeps input order inside each shard,
 // which insert routing needs for last-writer-in-batch-order semantics):
@@ -215,12 +268,14 @@ constexpr int kRouteTile = kT * kRoutePer;
 //   (keymax, nullable: a routed insert's batch -- a kKeyMax key sets the
 //   flag, and the scan then rejects the batch whole: every count 0, the
 //   error bit kErrKeyMax, as a local insert rejects its chunk)
-__global__ __launch_bounds__(kT) void k_route_count(const uint64_t* __restrict__ keys,
-                                                    uint64_t n, uint32_t shards,
-                                                    uint32_t* __restrict__ cm,
-                                                    uint32_t* keymax) {
+template <int M>
+__device__ __forceinline__ void route_count(const uint64_t* __restrict__ keys, uint64_t n,
+                                            uint32_t shards, uint32_t* __restrict__ cm,
+                                            uint32_t* keymax, const RouteSplit& sp) {
   __shared__ uint32_t c[kRouteMaxShards];
+  uint64_t* const sl = split_lds<M>();
   if (threadIdx.x < kRouteMaxShards) c[threadIdx.x] = 0;
+  split_stage<M>(sl, sp, shards);
   __syncthreads();
   const uint64_t base = (uint64_t)blockIdx.x * kRouteTile;
   bool bad = false;
@@ -230,12 +285,25 @@ __global__ __launch_bounds__(kT) void k_route_count(const uint64_t* __restrict__
     if (i < n) {
       const uint64_t k = keys[i];
       bad |= k == kKeyMax;
-      atomicAdd(&c[owner_of(k, shards)], 1u);
+      atomicAdd(&c[owner_by<M>(k, shards, sp, sl)], 1u);
     }
   }
   if (keymax && ballot(bad) && lane_id() == 0) atomicOr(keymax, 1u);
   __syncthreads();
   if (threadIdx.x < shards) cm[(uint64_t)blockIdx.x * shards + threadIdx.x] = c[threadIdx.x];
+}
+__global__ __launch_bounds__(kT) void k_route_count(const uint64_t* __restrict__ keys,
+                                                    uint64_t n, uint32_t shards,
+                                                    uint32_t* __restrict__ cm,
+                                                    uint32_t* keymax) {
+  route_count<kOwnSlices>(keys, n, shards, cm, keymax, RouteSplit{});
+}
+template <int M>
+__global__ __launch_bounds__(kT) void k_route_count_b(const uint64_t* __restrict__ keys,
+                                                      uint64_t n, uint32_t shards,
+                                                      uint32_t* __restrict__ cm, uint32_t* keymax,
+                                                      const RouteSplit sp) {
+  route_count<M>(keys, n, shards, cm, keymax, sp);
 }
 
 __global__ __launch_bounds__(1024) void k_route_scan(uint32_t* __restrict__ cm, uint32_t tiles,
@@ -290,15 +358,17 @@ __global__ __launch_bounds__(1024) void k_route_scan(uint32_t* __restrict__ cm, 
   }
 }
 
-__global__ __launch_bounds__(kT) void k_route_scatter(const uint64_t* __restrict__ keys,
-                                                      uint64_t n, uint32_t shards,
-                                                      const uint32_t* __restrict__ cm,
-                                                      uint64_t* __restrict__ keys_out,
-                                                      uint32_t* __restrict__ perm) {
+template <int M>
+__device__ __forceinline__ void route_scatter(const uint64_t* __restrict__ keys, uint64_t n,
+                                              uint32_t shards, const uint32_t* __restrict__ cm,
+                                              uint64_t* __restrict__ keys_out,
+                                              uint32_t* __restrict__ perm, const RouteSplit& sp) {
   constexpr int kW = kT / kWave;
   __shared__ uint32_t wc[kRoutePer][kW][kRouteMaxShards];
+  uint64_t* const sl = split_lds<M>();
   const int t = threadIdx.x, w = t >> 6, lane = lane_id();
   for (int j = t; j < kRoutePer * kW * kRouteMaxShards; j += kT) (&wc[0][0][0])[j] = 0;
+  split_stage<M>(sl, sp, shards);
   __syncthreads();
   const uint64_t base = (uint64_t)blockIdx.x * kRouteTile;
   uint64_t kk[kRoutePer];
@@ -308,7 +378,7 @@ __global__ __launch_bounds__(kT) void k_route_scatter(const uint64_t* __restrict
     const uint64_t i = base + (uint64_t)r * kT + t;
     const bool valid = i < n;
     kk[r] = valid ? keys[i] : 0;
-    own[r] = valid ? owner_of(kk[r], shards) : ~0u;
+    own[r] = valid ? owner_by<M>(kk[r], shards, sp, sl) : ~0u;
     rank[r] = 0;
     uint64_t pending = ballot(valid);
     while (pending) {  // one pass per distinct owner in this wave
@@ -338,22 +408,67 @@ __global__ __launch_bounds__(kT) void k_route_scatter(const uint64_t* __restrict
     perm[o] = (uint32_t)(base + (uint64_t)r * kT + t);
   }
 }
+__global__ __launch_bounds__(kT) void k_route_scatter(const uint64_t* __restrict__ keys,
+                                                      uint64_t n, uint32_t shards,
+                                                      const uint32_t* __restrict__ cm,
+                                                      uint64_t* __restrict__ keys_out,
+                                                      uint32_t* __restrict__ perm) {
+  route_scatter<kOwnSlices>(keys, n, shards, cm, keys_out, perm, RouteSplit{});
+}
+template <int M>
+__global__ __launch_bounds__(kT) void k_route_scatter_b(const uint64_t* __restrict__ keys,
+                                                        uint64_t n, uint32_t shards,
+                                                        const uint32_t* __restrict__ cm,
+                                                        uint64_t* __restrict__ keys_out,
+                                                        uint32_t* __restrict__ perm,
+                                                        const RouteSplit sp) {
+  route_scatter<M>(keys, n, shards, cm, keys_out, perm, sp);
+}
 
 uint64_t route_scratch_words(uint64_t n_max) {
   return ((n_max + kRouteTile - 1) / kRouteTile) * kRouteMaxShards;
 }
 
+// the form of the owner search for P shards with splitters: LDS unless the
+// caller names the kernel-argument form (mode 1, P <= 16).  Placing 2^20 keys
+// took 12.55 / 13.83 us from LDS against 13.08 / 14.12 us from the kernel
+// arguments at P = 8 / 16 (equal slices: 12.0 / 13.1 us), and the bucketing
+// 19.0 / 26.0 against 20.0 / 26.5 us (tools/route_bounds.py,
+// profiles/route_bounds.json): the unrolled compares cost more issue slots
+// than the three or four LDS reads they save
+static int own_mode(uint32_t P, int mode) {
+  return mode == kOwnArgs && P <= kRouteArgShards ? kOwnArgs : kOwnLds;
+}
+
 void launch_route_bucket(const uint64_t* keys, uint64_t n, uint32_t shards,
                          uint64_t* counts, uint64_t* keys_out, uint32_t* perm,
-                         uint32_t* cm, uint32_t* keymax, uint32_t* err, hipStream_t s) {
+                         uint32_t* cm, uint32_t* keymax, uint32_t* err, hipStream_t s,
+                         const RouteSplit* split, int mode) {
   const uint32_t tiles = (uint32_t)((n + kRouteTile - 1) / kRouteTile);
-  if (n)
-    hipLaunchKernelGGL(k_route_count, dim3(tiles), dim3(kT), 0, s, keys, n, shards, cm, keymax);
+  const int m = split ? own_mode(shards, mode) : kOwnSlices;
+  if (n) {
+    if (m == kOwnSlices)
+      hipLaunchKernelGGL(k_route_count, dim3(tiles), dim3(kT), 0, s, keys, n, shards, cm, keymax);
+    else if (m == kOwnArgs)
+      hipLaunchKernelGGL(k_route_count_b<kOwnArgs>, dim3(tiles), dim3(kT), 0, s, keys, n, shards,
+                         cm, keymax, *split);
+    else
+      hipLaunchKernelGGL(k_route_count_b<kOwnLds>, dim3(tiles), dim3(kT), 0, s, keys, n, shards,
+                         cm, keymax, *split);
+  }
   hipLaunchKernelGGL(k_route_scan, dim3(1), dim3(1024), 0, s, cm, tiles, shards, counts, keymax,
                      err);
-  if (n)
-    hipLaunchKernelGGL(k_route_scatter, dim3(tiles), dim3(kT), 0, s, keys, n, shards,
-                       (const uint32_t*)cm, keys_out, perm);
+  if (n) {
+    if (m == kOwnSlices)
+      hipLaunchKernelGGL(k_route_scatter, dim3(tiles), dim3(kT), 0, s, keys, n, shards,
+                         (const uint32_t*)cm, keys_out, perm);
+    else if (m == kOwnArgs)
+      hipLaunchKernelGGL(k_route_scatter_b<kOwnArgs>, dim3(tiles), dim3(kT), 0, s, keys, n, shards,
+                         (const uint32_t*)cm, keys_out, perm, *split);
+    else
+      hipLaunchKernelGGL(k_route_scatter_b<kOwnLds>, dim3(tiles), dim3(kT), 0, s, keys, n, shards,
+                         (const uint32_t*)cm, keys_out, perm, *split);
+  }
 }
 
 // out[i] = in[perm[i]] (apply the bucket permutation to a companion array)
@@ -425,21 +540,22 @@ __global__ __launch_bounds__(kT) void k_route_fill(uint64_t* out, uint64_t cap, 
 // list (ovk == nullptr) it finds nothing and kErrOverflow is reported.
 constexpr int kSlotT = 1024;
 
-template <int kSlotPer>
-__global__ __launch_bounds__(kSlotT) void k_route_slots(const uint64_t* __restrict__ keys,
-                                                        uint64_t n, uint32_t P, uint64_t cap,
-                                                        uint32_t* __restrict__ cursor,
-                                                        uint32_t* __restrict__ ctr,
-                                                        uint64_t* __restrict__ out,
-                                                        uint32_t* __restrict__ spos, uint64_t* ovk,
-                                                        uint32_t* ovi, uint32_t* err, uint32_t own_p,
-                                                        uint64_t* own_out) {
+template <int kSlotPer, int M>
+__device__ __forceinline__ void route_slots(const uint64_t* __restrict__ keys, uint64_t n,
+                                            uint32_t P, uint64_t cap,
+                                            uint32_t* __restrict__ cursor,
+                                            uint32_t* __restrict__ ctr, uint64_t* __restrict__ out,
+                                            uint32_t* __restrict__ spos, uint64_t* ovk,
+                                            uint32_t* ovi, uint32_t* err, uint32_t own_p,
+                                            uint64_t* own_out, const RouteSplit& sp) {
   constexpr int kW = kSlotT / kWave;
   constexpr int kSlotTile = kSlotT * kSlotPer;
   __shared__ uint32_t wc[kSlotPer][kW][kRouteMaxShards];
   __shared__ uint32_t last;
+  uint64_t* const sl = split_lds<M>();
   const int t = threadIdx.x, w = t >> 6, lane = lane_id();
   for (int j = t; j < kSlotPer * kW * kRouteMaxShards; j += kSlotT) (&wc[0][0][0])[j] = 0;
+  split_stage<M>(sl, sp, P);
   const uint64_t base = (uint64_t)blockIdx.x * kSlotTile;
   uint64_t kk[kSlotPer];
 #pragma unroll
@@ -459,7 +575,7 @@ __global__ __launch_bounds__(kSlotT) void k_route_slots(const uint64_t* __restri
 #pragma unroll
   for (int r = 0; r < kSlotPer; ++r) {
     const bool valid = base + (uint64_t)r * kSlotT + t < n;
-    own[r] = valid ? owner_of(kk[r], P) : ~0u;
+    own[r] = valid ? owner_by<M>(kk[r], P, sp, sl) : ~0u;
     const uint64_t vm = ballot(valid);
     uint64_t mine = vm, mine_o = vm;
     for (int b = 0; b < nb; ++b) {
@@ -546,6 +662,31 @@ __global__ __launch_bounds__(kSlotT) void k_route_slots(const uint64_t* __restri
     if ((uint32_t)t <= P) cursor[t] = v;
   }
 }
+template <int kSlotPer>
+__global__ __launch_bounds__(kSlotT) void k_route_slots(const uint64_t* __restrict__ keys,
+                                                        uint64_t n, uint32_t P, uint64_t cap,
+                                                        uint32_t* __restrict__ cursor,
+                                                        uint32_t* __restrict__ ctr,
+                                                        uint64_t* __restrict__ out,
+                                                        uint32_t* __restrict__ spos, uint64_t* ovk,
+                                                        uint32_t* ovi, uint32_t* err, uint32_t own_p,
+                                                        uint64_t* own_out) {
+  route_slots<kSlotPer, kOwnSlices>(keys, n, P, cap, cursor, ctr, out, spos, ovk, ovi, err, own_p,
+                                    own_out, RouteSplit{});
+}
+template <int kSlotPer, int M>
+__global__ __launch_bounds__(kSlotT) void k_route_slots_b(const uint64_t* __restrict__ keys,
+                                                          uint64_t n, uint32_t P, uint64_t cap,
+                                                          uint32_t* __restrict__ cursor,
+                                                          uint32_t* __restrict__ ctr,
+                                                          uint64_t* __restrict__ out,
+                                                          uint32_t* __restrict__ spos,
+                                                          uint64_t* ovk, uint32_t* ovi,
+                                                          uint32_t* err, uint32_t own_p,
+                                                          uint64_t* own_out, const RouteSplit sp) {
+  route_slots<kSlotPer, M>(keys, n, P, cap, cursor, ctr, out, spos, ovk, ovi, err, own_p, own_out,
+                           sp);
+}
 
 // fill: pad the runs with kKeyMax first (a slot's first batch, or one whose
 // capacity changed); otherwise the runs' tails keep the keys an earlier
@@ -555,16 +696,23 @@ __global__ __launch_bounds__(kSlotT) void k_route_slots(const uint64_t* __restri
 void launch_route_slots(const uint64_t* keys, uint64_t n, uint32_t P, uint64_t cap,
                         uint32_t* cursor, uint32_t* ctr, uint64_t* out, uint32_t* spos,
                         uint64_t* ovk, uint32_t* ovi, uint32_t* err, hipStream_t s, uint32_t own,
-                        uint64_t* own_out, bool fill) {
+                        uint64_t* own_out, bool fill, const RouteSplit* split, int mode) {
   const uint64_t slots = (uint64_t)P * cap;
   if (fill)
     hipLaunchKernelGGL(k_route_fill, grid1(slots + 1), dim3(kT), 0, s, out, cap, cursor, P, own,
                        own_out);
   // four keys per thread: 256 blocks for 2^20 keys (one or two keys per
   // thread, or eight, measured no better at P = 8: tools/route_p8.py)
-  if (n)
+  const int m = split ? own_mode(P, mode) : kOwnSlices;
+  if (n && m == kOwnSlices)
     hipLaunchKernelGGL(k_route_slots<4>, grid1(n, kSlotT * 4), dim3(kSlotT), 0, s, keys, n, P,
                        cap, cursor, ctr, out, spos, ovk, ovi, err, own, own_out);
+  else if (n && m == kOwnArgs)
+    hipLaunchKernelGGL((k_route_slots_b<4, kOwnArgs>), grid1(n, kSlotT * 4), dim3(kSlotT), 0, s,
+                       keys, n, P, cap, cursor, ctr, out, spos, ovk, ovi, err, own, own_out, *split);
+  else if (n)
+    hipLaunchKernelGGL((k_route_slots_b<4, kOwnLds>), grid1(n, kSlotT * 4), dim3(kSlotT), 0, s,
+                       keys, n, P, cap, cursor, ctr, out, spos, ovk, ovi, err, own, own_out, *split);
   else if (!fill)
     (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (P + 1), s);
 }
@@ -687,7 +835,9 @@ __global__ __launch_bounds__(kT) void k_range_pieces(const uint64_t* from, const
     const uint64_t f = from[j], t = to[j];
     const uint64_t slo = bnd.b[p];
     const uint64_t shi = p + 1 < P ? bnd.b[p + 1] - 1 : kKeyMax;  // inclusive top
-    if (f <= t && f <= shi && t >= slo) {
+    // repeated splitters: shard [x, x) owns nothing (its top would wrap for x = 0)
+    const bool none = p + 1 < P && bnd.b[p + 1] <= slo;
+    if (!none && f <= t && f <= shi && t >= slo) {
       lo = f > slo ? f : slo;
       hi = t < shi ? t : shi;
     }

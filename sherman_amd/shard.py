@@ -35,13 +35,6 @@ Python exchange below remains the logic the gloo tests check.
 import torch
 
 
-def owner_of(keys, world):
-    """floor(k * P / 2^64) for u64 keys held as int64 (== __umul64hi(k, P))."""
-    hi = (keys >> 32) & 0xFFFFFFFF
-    lo = keys & 0xFFFFFFFF
-    return (hi * world + ((lo * world) >> 32)) >> 32
-
-
 _SIGN = -(1 << 63)  # int64 bit pattern of 2^63
 
 
@@ -50,9 +43,42 @@ def _u64(x):
     return x - (1 << 64) if x >= (1 << 63) else x
 
 
-def shard_bounds(world, device):
-    """int64 tensor of the P + 1 u64 shard boundaries ceil(s * 2^64 / P)."""
-    b = [_u64((s * (1 << 64) + world - 1) // world) for s in range(world)] + [_u64((1 << 64) - 1)]
+def _split_list(splitters, world):
+    """The P - 1 splitters as Python ints in [0, 2^64) (from ints, numpy u64
+    or an int64 tensor holding the bits)."""
+    if torch.is_tensor(splitters):
+        splitters = splitters.tolist()
+    sp = [int(x) & ((1 << 64) - 1) for x in splitters]
+    if len(sp) != world - 1:
+        raise ValueError("world - 1 splitters")
+    if any(a > b for a, b in zip(sp, sp[1:])) or (sp and sp[-1] == (1 << 64) - 1):
+        raise ValueError("splitters ascend and none is 2^64 - 1")
+    return sp
+
+
+def owner_of(keys, world, splitters=None):
+    """The owning shard of u64 keys held as int64.  Equal slices: floor(k * P /
+    2^64) (== __umul64hi(k, P)).  With splitters (P - 1 ascending u64
+    boundaries, repeats allowed): the number of splitters <= k, so a key equal
+    to a repeated splitter goes to the highest shard that starts there."""
+    if splitters is not None:
+        sp = torch.tensor([_u64(x) ^ _SIGN for x in _split_list(splitters, world)],
+                          dtype=torch.int64, device=keys.device)
+        # the sign bit flipped: signed order of the int64 = unsigned order of the u64
+        return torch.bucketize(keys ^ _SIGN, sp, right=True)
+    hi = (keys >> 32) & 0xFFFFFFFF
+    lo = keys & 0xFFFFFFFF
+    return (hi * world + ((lo * world) >> 32)) >> 32
+
+
+def shard_bounds(world, device, splitters=None):
+    """int64 tensor of the P + 1 u64 shard boundaries: 0, then the splitters
+    (default ceil(s * 2^64 / P)), then 2^64 - 1 standing for the top."""
+    if splitters is not None:
+        inner = _split_list(splitters, world)
+    else:
+        inner = [(s * (1 << 64) + world - 1) // world for s in range(1, world)]
+    b = [0] + [_u64(x) for x in inner] + [_u64((1 << 64) - 1)]
     return torch.tensor(b, dtype=torch.int64, device=device)
 
 
@@ -73,10 +99,60 @@ def shard_range(rank, world):
     return lo, bits
 
 
+def sample_splitters(keys, world, dist, group=None, per_rank=1024):
+    """P - 1 splitters for a first load, from a sample (plain torch plumbing;
+    a collective over `dist`): every rank sorts its u64 keys (int64 tensor)
+    and takes per_rank of them at even strides, the ranks all-gather the
+    samples, and the result is the j / P quantiles (j = 1 .. P - 1) of the
+    merged sample, each sample key weighted by the keys it stands for.  With s
+    sample keys in all, a shard's share of the keys is off by about P / s of
+    N / P at most (one stride on either side); the default keeps that under a
+    few percent for P <= 16.  Returns Python ints, the same on every rank."""
+    n, dev = keys.numel(), keys.device
+    srt = torch.sort(keys ^ _SIGN).values  # unsigned order
+    m = min(n, per_rank)
+    if m:
+        # the last key of each of m equal strides
+        idx = ((torch.arange(1, m + 1, device=dev, dtype=torch.int64) * n) // m) - 1
+        smp = srt[idx]
+    else:
+        smp = srt[:0]
+    buf = torch.zeros(per_rank + 2, dtype=torch.int64, device=dev)
+    buf[0], buf[1] = n, m
+    buf[2:2 + m] = smp
+    got = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(got, buf, group=group)
+    ks, ws = [], []
+    for g in got:
+        gn, gm = int(g[0]), int(g[1])
+        if gm:
+            ks.append(g[2:2 + gm])
+            ws.append(torch.full((gm,), gn / gm, dtype=torch.float64, device=dev))
+    if not ks:
+        return [0] * (world - 1)
+    k, w = torch.cat(ks), torch.cat(ws)
+    o = torch.argsort(k, stable=True)
+    k, cw = k[o], torch.cumsum(w[o], 0)
+    total = float(cw[-1])
+    out = []
+    for j in range(1, world):
+        # the first sample key with j / P of the weight at or below it: keys
+        # up to and including it stay left, so the boundary is that key + 1
+        i = int(torch.searchsorted(cw, torch.tensor(total * j / world - 1e-9, dtype=torch.float64,
+                                                    device=dev)))
+        i = min(i, k.numel() - 1)
+        v = (int(k[i]) ^ _SIGN) & ((1 << 64) - 1)
+        out.append(min(v + 1, (1 << 64) - 2))
+    return out
+
+
 class ShardRouter:
-    def __init__(self, local, world, dist, group=None, cshard=None):
+    def __init__(self, local, world, dist, group=None, cshard=None, splitters=None):
         self.local, self.world, self.dist, self.group = local, world, dist, group
         self.cshard = cshard
+        # the shards' boundaries (None: equal slices); with a C shard they are
+        # the shard's own (CShard.set_splitters / rebalance)
+        self.splitters = None if splitters is None else _split_list(splitters, world)
         self._bufs = {}
         self._pending = False  # a search_begin not yet ended (it owns kb / perm)
 
@@ -99,7 +175,10 @@ class ShardRouter:
         # a fresh buffer per batch, so a pending batch keeps its own counts
         cnts = torch.empty(2 * self.world, dtype=torch.int64, device=dev)
         cnt, rcnt = cnts[:self.world], cnts[self.world:2 * self.world]
-        self.local.route_bucket(keys, self.world, kb, perm, cnt)
+        if self.splitters is None:
+            self.local.route_bucket(keys, self.world, kb, perm, cnt)
+        else:
+            self.local.route_bucket(keys, self.world, kb, perm, cnt, splitters=self.splitters)
         self._a2a(rcnt, cnt)
         return kb, perm, cnts
 
@@ -204,11 +283,17 @@ class ShardRouter:
         if self.cshard is not None:
             return self.cshard.range_query(lo, hi, n_cap)
         n, dev, P = lo.numel(), lo.device, self.world
-        bnd = shard_bounds(P, dev)
+        bnd = shard_bounds(P, dev, self.splitters)
         first = bnd[:P]
         last = torch.cat([bnd[1:P] - 1, bnd[P:P + 1]])  # inclusive top of shard s
         plo = umax(lo.unsqueeze(0).expand(P, n), first.unsqueeze(1).expand(P, n)).contiguous()
         phi = umin(hi.unsqueeze(0).expand(P, n), last.unsqueeze(1).expand(P, n)).contiguous()
+        if self.splitters is not None and P > 1:
+            # repeated splitters: shard [x, x) owns nothing (its top would wrap for x = 0)
+            none = torch.cat([(bnd[1:P] ^ _SIGN) <= (bnd[:P - 1] ^ _SIGN),
+                              torch.zeros(1, dtype=torch.bool, device=dev)]).unsqueeze(1)
+            plo = torch.where(none, torch.ones_like(plo), plo)
+            phi = torch.where(none, torch.zeros_like(phi), phi)
         # scan counts of every rank (receive splits)
         cn = torch.full((2 * P,), n, dtype=torch.int64, device=dev)
         self._a2a(cn[P:], cn[:P])

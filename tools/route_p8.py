@@ -6,7 +6,10 @@ all of them, so the walk has a 2^27-key shard's cost), the gather of the
 results to input order (shm__route_gather) -- timed with HIP events on one
 stream against the plain local walk of the same queries.  The exchange
 itself (RCCL over xGMI) is not in either number.
-usage: python tools/route_p8.py [keys_log2] [steps] [P]"""
+With split = 1 the placement routes by splitters (the equal slices' own
+boundaries, so the runs are the same; shm__route_slots_bounds), 2 names the
+LDS form of the owner search (tools/route_bounds.py times the placement alone).
+usage: python tools/route_p8.py [keys_log2] [steps] [P] [split]"""
 import ctypes
 import json
 import math
@@ -21,6 +24,7 @@ import sherman_amd as shm
 kl = int(sys.argv[1]) if len(sys.argv) > 1 else 27
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 P = int(sys.argv[3]) if len(sys.argv) > 3 else 8
+split = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 torch.cuda.set_device(0)
 n_keys, batch = 1 << kl, 1 << 20
 cap = batch // P + 6 * int(math.sqrt(batch // P)) + 256  # shard.cpp get_slot_cap
@@ -51,6 +55,18 @@ L.shm__route_slots_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uin
 L.shm__route_gather.restype = ctypes.c_int
 L.shm__route_gather.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+if split:
+    L.shm__route_slots_bounds.restype = ctypes.c_int
+    L.shm__route_slots_bounds.argtypes = L.shm__route_slots_ex.argtypes[:11] + [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    bounds = (ctypes.c_uint64 * max(P - 1, 1))(*[((p << 64) + P - 1) // P for p in range(1, P)])
+    slots_ex = L.shm__route_slots_ex
+
+    def slots_split(t_, k_, n_, P_, cap_, cur_, sl_, sp_, ok_, oi_, fill_, st_):
+        return L.shm__route_slots_bounds(t_, k_, n_, P_, cap_, cur_, sl_, sp_, ok_, oi_, fill_,
+                                         bounds, 2 if split == 2 else 0, st_)
+
+    L.shm__route_slots_ex = slots_split
 sp = torch.cuda.current_stream().cuda_stream
 cursor = torch.zeros(P + 1, dtype=torch.int32, device="cuda")
 slots = torch.empty(P * cap, dtype=torch.int64, device="cuda")
@@ -182,6 +198,7 @@ torch.cuda.synchronize()
 assert torch.equal(out, v) and torch.equal(fnd, f), "routed results differ from the local get"
 assert int(cursor[P].item()) == 0, "overflow at this capacity"
 print(json.dumps({"keys": n_keys, "batch": batch, "P": P, "cap": cap, "steps": steps,
+                  "split": split,
                   "local_us_per_step": round(min(us_local, us_local2), 2),
                   "routed_us_per_step": round(us_routed, 2),
                   "overhead_us": round(us_routed - min(us_local, us_local2), 2),
