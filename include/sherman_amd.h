@@ -201,6 +201,10 @@ int shm_insert_batch_async(shm_tree *t, const uint64_t *keys, const uint64_t *va
  * until the device has finished with them (flow control: a pipelined caller
  * stays about two chunks ahead of the device; after 2 s it queues a
  * device-side wait instead and returns).
+ * Once per 2^32 - 1 chunks (see shm_last_chunk) shm_insert_order returns
+ * SHM_EAGAIN with a single ticket outstanding: the chunk ids start over and
+ * the chunk of that ticket must be applied under its old id first.  Apply it
+ * and call again.
  * Errors are reported as for shm_insert_batch_async.  Tree::insert
  * (src/Tree.cpp:353-403) for a batch, as shm_insert_batch_async. */
 int shm_insert_order(shm_tree *t, const uint64_t *keys, const uint64_t *vals, uint64_t n,
@@ -436,7 +440,16 @@ typedef struct shm_error_t {
 } shm_error_t;
 int shm_last_error(shm_tree *t, shm_error_t *out, int reset);
 /* id of the last insert chunk queued on the handle (1, 2, ...; a batch of n
- * ops is ceil(n / max_batch) chunks) */
+ * ops is ceil(n / max_batch) chunks).  The id is also the tag the device
+ * state is stamped with, 32 bits wide: the chunk after id 2^32 - 1 gets id 1
+ * again, never 0.  Before it is issued the handle is drained (a device
+ * synchronisation inside that insert call) and every word that carries a
+ * chunk tag is cleared, so ids of the two epochs are never compared on the
+ * device.  shm_last_chunk and shm_error_t.chunk count within the epoch: a
+ * caller that pairs them must read both on the same side of the restart (the
+ * restart is visible as shm_last_chunk going down); an error bit set before
+ * the restart and read after it names its chunk by the old epoch's id.  The
+ * contents, statuses and error bits of every chunk are unaffected. */
 uint32_t shm_last_chunk(shm_tree *t);
 /* Copy `bytes` (a multiple of 4, <= 1024) of device memory at `src` to
  * host_out once the work queued on `stream` before it has produced them,

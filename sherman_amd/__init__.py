@@ -788,6 +788,14 @@ class Tree:
         _check(_hooks().shm__get_forms(self.h, -1 if coop is None else int(bool(coop)),
                                        -1 if pack is None else int(bool(pack))), "get_forms")
 
+    def seq_jump(self, which, value):
+        """Test hook (shm__seq_jump): move the insert chunk counter ("chunk")
+        or the scan counter ("scan") forward to `value`, as if that many
+        chunks or scans without effect had run (tree.cpp lists every word it
+        sets).  Waits for the tree; ShermanError(SHM_EINVAL) while ordered
+        chunks are pending or when value is below the counter."""
+        _check(_hooks().shm__seq_jump(self.h, {"chunk": 0, "scan": 1}[which], value), "seq_jump")
+
     def dir_verify(self):
         """Diagnostics (shm__dir_verify): every directory entry the walks
         trust checked against the tree as it is now."""
@@ -934,6 +942,7 @@ _HOOKS = [
     ("shm__vt_stats", ctypes.c_int, [vp, ctypes.POINTER(u64)]),
     ("shm__vt_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
     ("shm__get_forms", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+    ("shm__seq_jump", ctypes.c_int, [vp, ctypes.c_int, u32]),
 ]
 
 

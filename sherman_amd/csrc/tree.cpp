@@ -27,6 +27,7 @@
 #include "../../include/sherman_amd.h"
 #include "kernels.h"
 #include "layout.h"
+#include "seq_epoch.h"
 
 using namespace shm;
 
@@ -1117,6 +1118,16 @@ int insert_apply(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag,
   // no page still carries this chunk's mark from 255 chunks ago
   if (dev::new_mark(tag) == 1)
     HIP_OK(hipMemsetAsync(t->pnew, 0, t->cap_pages, s));
+  // the fan-in words' 32-bit tag (split_wave.h fan_tag: the chunk tag's low
+  // 29 bits and the level) repeats every 2^29 chunks: clear the words when it
+  // wraps, so a large split never finds the count its segment's word was
+  // left with 2^29 chunks ago under the same tag (fan_arrive would count on
+  // from it and fan_in pass early or never).  A zero word reads as tag 0
+  // with no arrival, which is what the chunk with tag bits 0 starts from
+  if ((tag & (seq::kFanPeriod - 1u)) == 0) {
+    HIP_OK(hipMemsetAsync(t->leaf_rd, 0, sizeof(uint64_t) * t->sep_cap, s));
+    HIP_OK(hipMemsetAsync(t->int_rd, 0, sizeof(uint64_t) * t->sep_cap, s));
+  }
   dev::WalkArgs w = walk_args(t);
   uint64_t* const cnt = op_counts(t, tag);
   w.keys = op_keys(t, tag);
@@ -1278,9 +1289,52 @@ int insert_apply(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag,
   return SHM_OK;
 }
 
+// The end of the chunk counter's epoch (seq_epoch.h kLastTag = 2^32 - 1): the
+// next chunk is tag 1 of a new epoch.  Every device word that is compared
+// with a chunk tag would otherwise meet values of the old epoch: lock words
+// stay above every small tag (never free: kErrLock after kMaxLockSpins), and
+// gate, skip, the segmentation's tile words, the ordering's look-back words
+// and the fan-in words could equal a new tag again.  So the handle is drained
+// and all of them are zeroed, as shm_tree_create leaves them, the page marks
+// with them; the counter restarts at 0 (the caller increments it to 1: tag 0
+// is never issued) and the mirrors follow: the superblock's batch count, the
+// host words (published tag, applied tag) and the flow control of
+// insert_order (app_valid), whose `<` wait would otherwise hold a small tag
+// against a large applied word of the old epoch and let it pass early.
+int epoch_reset(shm_tree* t) {
+  HIP_OK(hipDeviceSynchronize());
+  mirror(t);  // exact: the device is idle
+  hipStream_t s = t->stream;
+  HIP_OK(hipMemsetAsync(t->locks, 0, sizeof(uint64_t) * t->cfg.num_locks, s));
+  HIP_OK(hipMemsetAsync(t->ctl, 0, sizeof(dev::UpperCtl), s));
+  HIP_OK(hipMemsetAsync(t->seg_lb, 0, sizeof(uint64_t) * (dev::seg_tiles(t->sep_cap) + 1), s));
+  HIP_OK(hipMemsetAsync(t->bins, 0, sizeof(uint32_t) * 4 * dev::kCoarse, s));
+  HIP_OK(hipMemsetAsync(t->leaf_rd, 0, sizeof(uint64_t) * t->sep_cap, s));
+  HIP_OK(hipMemsetAsync(t->int_rd, 0, sizeof(uint64_t) * t->sep_cap, s));
+  HIP_OK(hipMemsetAsync(t->pnew, 0, t->cap_pages, s));
+  // k_locate's "a page was marked" word (d_counts + 10) holds a chunk tag too
+  HIP_OK(hipMemsetAsync(t->d_counts, 0, sizeof(uint64_t) * 32, s));
+  t->chunks = 0;
+  for (int p = 0; p < 2; ++p) {
+    t->app_valid[p] = false;
+    t->app_tag[p] = 0;
+  }
+  reinterpret_cast<volatile uint64_t*>(t->h_pin)[kPubWord / 2 + dev::kPubApplied] = 0;
+  if (write_superblock(t, s)) return SHM_EIO;  // batches = 0, and the host words (publish_host)
+  t->pub_batch = t->pub_seen = 0;
+  t->dir_last_upkept = false;  // both parities' repair list counts are unknown again
+  HIP_OK(hipStreamSynchronize(s));
+  return SHM_OK;
+}
+
 // the chunk's ordering (step 1): its tag, profile record started
 int insert_begin(shm_tree* t, hipStream_t s, const uint64_t* keys, const uint64_t* vals,
                  uint64_t n, bool skip_pad, uint32_t* tag, shm_tree::ProfRec& pr) {
+  if (seq::epoch_ends(t->chunks)) {
+    // a chunk ordered in the old epoch is applied under its old tag first
+    if (t->n_pend) return SHM_EAGAIN;
+    if (const int rc = epoch_reset(t)) return rc;
+  }
   *tag = ++t->chunks;
   if (t->prof_on) {
     const int rc = prof_begin(t, s, shm_tree::kProfInsert, n, 4, pr);
@@ -2237,6 +2291,107 @@ int shm__upper_force(shm_tree* t, uint32_t flags) {
   return SHM_OK;
 }
 int shm__upper_force_abort(shm_tree* t) { return shm__upper_force(t, 1u); }
+
+// Test hook, not part of include/sherman_amd.h: move a counter forward as if
+// value - current chunks (which = 0) or scans (which = 1) without effect had
+// run -- chunks that only overwrite stored keys with the values they hold (no
+// new key, no delete, none rejected, directory not kept), scans of one tile.
+// Waits for the tree first.  SHM_EINVAL while ordered chunks are pending or
+// when value is below the counter; value == counter changes nothing.
+//
+// which = 0, the chunk counter (C = the counter, V = value).  Set on the host:
+//   t->chunks = V                   the counter (shm_last_chunk)
+//   host word 0 (publish_host)      the published tag; pub_batch, pub_seen = V
+//                                   (only compared with each other: no quiet-
+//                                   rule look is pending)
+//   host word kPubApplied = V       the last skipped chunk is done with its op
+//                                   buffers; app_valid = false says the same
+//                                   to insert_order (nothing to wait for)
+//   dir_last_upkept = false         no skipped chunk kept the directory: the
+//                                   next kept chunk zeroes its parity's
+//                                   repair list count itself
+// The host clears the skipped chunks' insert_apply would have made:
+//   pnew            when a multiple of 255 lies in (C, V] (the marks' period);
+//                   the chunks after it bring no new key and mark nothing
+//   leaf_rd, int_rd when a multiple of 2^29 lies in (C, V] (the fan tags')
+// Device words the skipped chunks would have rewritten, written here:
+//   superblock.batches = V          every chunk's completion stores it (the
+//                                   whole superblock is rewritten from the
+//                                   exact mirror: no other field changes)
+//   UpperCtl tk, dn, abort, leaf_np, leaf_ns, leaf_nb, alloc, made, root_new,
+//   lvl_sep, done, ualloc, late     both parities zero: chunk C + 1 zeroes
+//                                   parity C & 1 (upper_zero_next) and no
+//                                   skipped chunk counts a split, so the next
+//                                   chunk finds its parity clean whether
+//                                   V - C is odd or even
+//   UpperCtl skip[V & 1] = V, skip[(V - 1) & 1] = V - 1 (if V - C >= 2), and
+//   ndel of those parities = 0      the segmentation completes such chunks
+//                                   (seg_complete_unchanged)
+//   the ordering's 256 look-back words = (V & 0xFFFF) << 48
+//                                   every k_bin_unique launch that is not
+//                                   rejected publishes all of them (isort.hip
+//                                   bin_prefix, called on both paths of every
+//                                   block); only the tag is compared later,
+//                                   so the counts are written as 0
+// Left as they are: gate (no skipped chunk is rejected), the lock words (a
+// skipped chunk would leave the words it took at its tag << 32, which is
+// free for every later tag exactly as the older value is), the
+// segmentation's tile words (a skipped chunk writes (tag << 32 | 0) into the
+// words of its own tiles only; an older tag matches a later chunk no more
+// than a skipped one would), the op buffers and the ordering's scratch
+// (rewritten by every ordering before they are read).
+//
+// which = 1, scan_seq: set to V, or V + 1 when V is a multiple of 2^16
+// (scan_tag steps over those); bsum64 is cleared when a multiple of 2^16
+// lies in (C, V], as scan_tag clears it.  A skipped scan of one tile reads
+// no tile word and leaves its own word 0 tagged: not written here, its tag
+// is older than any the next 65534 scans use.
+int shm__seq_jump(shm_tree* t, int which, uint32_t value) {
+  if (!t || (which != 0 && which != 1)) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  HIP_OK(hipDeviceSynchronize());
+  mirror(t);  // exact: the device is idle
+  if (which == 1) {
+    if (value < t->scan_seq) return SHM_EINVAL;
+    const seq::ScanJump j = seq::scan_jump(t->scan_seq, value);
+    if (j.clear)
+      HIP_OK(hipMemset(t->bsum64, 0, sizeof(uint64_t) * (dev::seg_tiles(t->nmax) + 1)));
+    t->scan_seq = j.seq;
+    return SHM_OK;
+  }
+  if (t->n_pend || value < t->chunks) return SHM_EINVAL;
+  const uint32_t cur = t->chunks;
+  if (value == cur) return SHM_OK;
+  const seq::ChunkJump j = seq::chunk_jump(cur, value);
+  if (j.marks) HIP_OK(hipMemset(t->pnew, 0, t->cap_pages));
+  if (j.fan) {
+    HIP_OK(hipMemset(t->leaf_rd, 0, sizeof(uint64_t) * t->sep_cap));
+    HIP_OK(hipMemset(t->int_rd, 0, sizeof(uint64_t) * t->sep_cap));
+  }
+  uint8_t* const ctl = reinterpret_cast<uint8_t*>(t->ctl);
+  HIP_OK(hipMemset(ctl, 0, offsetof(dev::UpperCtl, gate)));
+  HIP_OK(hipMemset(ctl + offsetof(dev::UpperCtl, leaf_np), 0,
+                   offsetof(dev::UpperCtl, skip) - offsetof(dev::UpperCtl, leaf_np)));
+  for (uint32_t k = 0; k < 2 && value - k > cur; ++k) {
+    const uint32_t v = value - k;
+    const uint64_t sk = v, nd = 0;
+    HIP_OK(hipMemcpy(&t->ctl->skip[v & 1u][0], &sk, sizeof(sk), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(&t->ctl->ndel[v & 1u][0], &nd, sizeof(nd), hipMemcpyHostToDevice));
+  }
+  {
+    std::vector<uint64_t> w((size_t)dev::kCoarse, (uint64_t)(value & 0xFFFFu) << 48);
+    HIP_OK(hipMemcpy(reinterpret_cast<uint64_t*>(t->bins + 2 * dev::kCoarse), w.data(),
+                     sizeof(uint64_t) * w.size(), hipMemcpyHostToDevice));
+  }
+  t->chunks = value;
+  for (int p = 0; p < 2; ++p) t->app_valid[p] = false;
+  reinterpret_cast<volatile uint64_t*>(t->h_pin)[kPubWord / 2 + dev::kPubApplied] = value;
+  if (write_superblock(t, t->stream)) return SHM_EIO;  // batches = V; publish_host: word 0 = V
+  t->pub_batch = t->pub_seen = value;
+  t->dir_last_upkept = false;
+  HIP_OK(hipStreamSynchronize(t->stream));
+  return SHM_OK;
+}
 
 // Diagnostics: the pages the last insert chunk's early splits took (its
 // upsert kernel's, upsert.hip), after synchronising the tree
