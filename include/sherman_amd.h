@@ -132,6 +132,14 @@ int shm_abi_version(void);
 /* batched hot path (device pointers) ------------------------------------------ */
 /* vals_out[i] = value of keys[i] (0 if absent); found_out[i] = 1/0.
  * found_out may be NULL. Reads only.
+ * The rule for every reader and every builder of an index that a reader
+ * trusts (the leaf directory, the key-value bucket table, the leaf summaries):
+ * NO DATA IS TAKEN FROM A PAGE THE TREE DOES NOT REACH FROM ITS ROOT (through
+ * child and sibling pointers).  Below pages_used such pages exist -- pages a
+ * failed take lost (shm_insert_batch, SHM_ENOMEM), pages of an earlier tree
+ * that a smaller shm_bulk_load or shm_load_image left behind, pages a loaded
+ * image carries along -- and their bytes may be those of a leaf with valid
+ * entries.  A get answers what the tree holds, whatever they hold.
  * Streams: searches issued on distinct streams may run concurrently on the
  * device (an ordered batch uses one of two internal workspaces, alternating,
  * so consecutive batches on two streams overlap one's ordering with the
@@ -306,7 +314,15 @@ int shm_stats(shm_tree *t, shm_stats_t *out);
 int shm_dump_image(shm_tree *t, void *host_buf, uint64_t cap,
                    uint64_t *bytes_used, uint64_t *root_ptr);
 /* Replace the tree with a page image laid out by the reference format
- * (pages at GlobalAddress offsets, nodeID == cfg.node_id). */
+ * (pages at GlobalAddress offsets, nodeID == cfg.node_id).  Every byte of the
+ * image is copied, so shm_dump_image gives it back; but the tree is what
+ * root_ptr reaches through child and sibling pointers, found by one walk
+ * over the host buffer (every reached page read once), and only the leaves
+ * it reaches are described to the readers' indexes.  A page the image merely
+ * carries along (see the rule at shm_search_batch) is never read as data,
+ * even where its bytes are those of a leaf.  Pointers to another node,
+ * outside the image or off a page boundary are not followed (shm_check
+ * reports such a tree). */
 int shm_load_image(shm_tree *t, const void *host_buf, uint64_t bytes,
                    uint64_t root_ptr);
 /* Bulk load: the tree of a sorted run of pairs, written in one pass.

@@ -930,11 +930,16 @@ void launch_top(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, uint6
                      keys, pages, scratch, n_out, err);
 }
 
-// summaries of a loaded image: one wave per page
+// summaries of a loaded image: one wave per page.  Only the leaves the image
+// reaches from its root (leaf[pg] != 0, the host's walk in shm_load_image) get
+// a line: the tag says "a current leaf of the tree" to the page sweeps
+// (leafdir.hip swept_leaf), and a page the tree does not reach is none,
+// whatever its bytes look like.  The host zeroed every line before.
 __global__ __launch_bounds__(256) void k_sum_rebuild(const uint8_t* arena, uint64_t pages,
+                                                     const uint8_t* __restrict__ leaf,
                                                      uint8_t* sum) {
   const uint64_t pg = 1 + ((uint64_t)blockIdx.x * 256 + threadIdx.x) / kWave;
-  if (pg >= pages) return;  // wave-uniform
+  if (pg >= pages || !leaf[pg]) return;  // wave-uniform
   const int lane = lane_id();
   const uint8_t* page = arena + pg * kPageSize;
   const u32x4* pw = reinterpret_cast<const u32x4*>(page);
@@ -956,11 +961,12 @@ __global__ __launch_bounds__(256) void k_sum_rebuild(const uint8_t* arena, uint6
   put_leaf_sum(sum, pg * kPageSize, highest, fp);
 }
 
-void launch_sum_rebuild(const uint8_t* arena, uint64_t pages, uint8_t* sum, hipStream_t s) {
+void launch_sum_rebuild(const uint8_t* arena, uint64_t pages, const uint8_t* leaf, uint8_t* sum,
+                        hipStream_t s) {
   if (pages <= 1) return;
   const uint64_t waves = pages - 1;
   hipLaunchKernelGGL(k_sum_rebuild, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, arena,
-                     pages, sum);
+                     pages, leaf, sum);
 }
 
 // G = 4 pages per group, NB = 1 group buffer, 4 waves per block: 16 KB of

@@ -131,8 +131,10 @@ uint64_t get_sum_blocks(uint64_t n);
 void launch_get_sum(const WalkArgs& a, uint64_t n, hipStream_t s, hipEvent_t ev0 = nullptr,
                     hipEvent_t ev1 = nullptr);
 // rebuild the summaries of pages [1, pages) from the page bytes (a loaded
-// image), one wave per page
-void launch_sum_rebuild(const uint8_t* arena, uint64_t pages, uint8_t* sum, hipStream_t s);
+// image), one wave per page; leaf[p] != 0 (device bytes, one per page) names
+// the leaves the image reaches from its root: only those get a line
+void launch_sum_rebuild(const uint8_t* arena, uint64_t pages, const uint8_t* leaf, uint8_t* sum,
+                        hipStream_t s);
 // header-only descent, lane = op (locate.hip): out_page[i] = the page of
 // a.target_level holding keys[i]; starts at the leaf directory for level 0
 void launch_locate(const WalkArgs& a, uint64_t n_upper, hipStream_t s);
@@ -151,16 +153,20 @@ void launch_leaf_dir(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, 
                      uint32_t* hint, int from_hint, const uint8_t* sum, uint32_t* err,
                      hipStream_t s, int pairs = 0);
 // the pairs of a pair-form directory: one wave per page of [1, n_pages)
-void launch_dir_pairs(const uint8_t* arena, uint64_t n_pages, uint16_t node, uint64_t dir_lo,
-                      uint32_t shift, uint64_t n_ent, uint64_t* dir, hipStream_t s);
+// whose summary line (sum) carries the leaf tag: the tree's current leaves
+void launch_dir_pairs(const uint8_t* arena, const uint8_t* sum, uint64_t n_pages, uint16_t node,
+                      uint64_t dir_lo, uint32_t shift, uint64_t n_ent, uint64_t* dir,
+                      hipStream_t s);
 // the value form after the pairs (layout.h kDirVals): one thread per entry
 void launch_dir_vals(const uint8_t* arena, uint64_t n_pages, uint64_t n_ent, uint64_t* dir,
                      hipStream_t s);
 // the key-value bucket table (valtab.h) from the leaves, after a zero fill:
-// one wave per page of [1, n_pages); ctr (zeroed by the caller) = {dead
-// buckets, stored keys that ended in dead buckets, stored keys}
-void launch_vt_build(const uint8_t* arena, uint64_t n_pages, uint64_t lo, uint32_t shift,
-                     uint64_t n_buckets, uint64_t* vt, uint64_t* ctr, hipStream_t s);
+// one wave per page of [1, n_pages) whose summary line (sum) carries the leaf
+// tag; ctr (zeroed by the caller) = {dead buckets, stored keys that ended in
+// dead buckets, stored keys}
+void launch_vt_build(const uint8_t* arena, const uint8_t* sum, uint64_t n_pages, uint64_t lo,
+                     uint32_t shift, uint64_t n_buckets, uint64_t* vt, uint64_t* ctr,
+                     hipStream_t s);
 // rebuild the entries an insert chunk listed (fix[0 .. fix_n[par]), at most
 // cap) from the tree, in form `form` (kDirForm*); zeroes fix_n[par ^ 1]; the
 // repairs past cap are added to *lost (host memory, nullable)

@@ -72,7 +72,12 @@ SHM_HD int hw_dma_lanes(uint32_t hw) {
 // a valid slot (value != 0), 0 for an empty one.  A get reads the line, turns
 // right on k >= highest (the sibling from the page header: a stale start,
 // rare), and reads only the entries whose fp matches (false positives
-// ~ 40 / 255 per leaf).  Every leaf writer keeps the line.  At 64 B per page
+// ~ 40 / 255 per leaf).  Every leaf writer keeps the line.  The tag is also
+// what tells a page sweep (leafdir.hip swept_leaf: the pair form's and the
+// bucket table's builds) a leaf of the tree from a page below next_page that
+// the tree does not reach: create zeroes every line, a bulk load clears the
+// lines of the pages it frees, a failed take writes none, and a loaded image
+// tags only the leaves its root reaches (tree.cpp image_leaves).  At 64 B per page
 // the lines of a 2^26-key shard (119 MB) and its leaf directory (64 MB) fit
 // the 256 MB Infinity Cache together.
 constexpr uint32_t kSumBytes = 64;

@@ -218,7 +218,25 @@ void launch_leaf_dir(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, 
 // fingerprint: 16 B of candidates for the ~4-9 keys of a prefix instead of
 // the fingerprints of every slot of its leaf (fewer false candidates), and
 // prefixes that span up to four leaves are answered the same way.
+//
+// Which pages are leaves of the tree: those whose summary line carries the
+// leaf tag (swept_leaf).  The page bytes alone do not say: below next_page
+// lie pages the tree does not reach (lost to a failed take, left by an
+// earlier tree, loaded with an image), and their bytes may be those of a
+// leaf with valid entries.  Every writer of a leaf sets the tag, a page that
+// stops being one loses it, and shm_load_image tags only what the image
+// reaches from its root (DESIGN §3.1 "Pages the tree does not reach").
+__device__ __forceinline__ bool swept_leaf(const uint8_t* __restrict__ arena,
+                                           const uint8_t* __restrict__ sum, uint64_t pi) {
+  // (both loads issued before either is tested: no dependent round more)
+  const uint8_t tag = sum[pi * kSumBytes + kSumOffTag];
+  const uint8_t* pg = arena + (pi << 10);
+  const bool leaf = pg[kOffLevel] == 0 && pg64_b1(pg, 2) == 0;  // level 0, no leftmost
+  return tag == kSumLeaf && leaf;
+}
+
 __global__ __launch_bounds__(256) void k_dir_pairs(const uint8_t* __restrict__ arena,
+                                                   const uint8_t* __restrict__ sum,
                                                    uint64_t n_pages, uint16_t node,
                                                    uint64_t dir_lo, uint32_t shift,
                                                    uint64_t n_ent, uint64_t* __restrict__ dir) {
@@ -227,7 +245,7 @@ __global__ __launch_bounds__(256) void k_dir_pairs(const uint8_t* __restrict__ a
   for (uint64_t pi = 1 + (uint64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
        pi < n_pages; pi += nw) {
     const uint8_t* pg = arena + (pi << 10);
-    if (pg[kOffLevel] != 0 || pg64_b1(pg, 2) != 0) continue;  // a leaf (no leftmost)
+    if (!swept_leaf(arena, sum, pi)) continue;
     if (lane >= kLeafCardinality) continue;
     uint64_t k, v;
     uint32_t f, r;
@@ -253,10 +271,11 @@ __global__ __launch_bounds__(256) void k_dir_pairs(const uint8_t* __restrict__ a
   }
 }
 
-void launch_dir_pairs(const uint8_t* arena, uint64_t n_pages, uint16_t node, uint64_t dir_lo,
-                      uint32_t shift, uint64_t n_ent, uint64_t* dir, hipStream_t s) {
+void launch_dir_pairs(const uint8_t* arena, const uint8_t* sum, uint64_t n_pages, uint16_t node,
+                      uint64_t dir_lo, uint32_t shift, uint64_t n_ent, uint64_t* dir,
+                      hipStream_t s) {
   if (n_pages <= 1 || !n_ent) return;
-  hipLaunchKernelGGL(k_dir_pairs, dim3(2048), dim3(256), 0, s, arena, n_pages, node, dir_lo,
+  hipLaunchKernelGGL(k_dir_pairs, dim3(2048), dim3(256), 0, s, arena, sum, n_pages, node, dir_lo,
                      shift, n_ent, dir);
 }
 
@@ -311,13 +330,15 @@ void launch_dir_vals(const uint8_t* arena, uint64_t n_pages, uint64_t n_ent, uin
 }
 
 // The key-value bucket table (valtab.h) of a read phase's build, after the
-// host's zero fill: one wave per page, as k_dir_pairs; every valid entry of a
+// host's zero fill: one wave per page, as k_dir_pairs (the tree's leaves are
+// the tagged pages, swept_leaf); every valid entry of a
 // leaf (value != 0, f == r: the entries a get can find) is stored by
 // vt_upsert.  ctr = {dead buckets, stored keys that ended in dead buckets,
 // stored keys}: a bucket dies once, by the lane whose exchange set the marker
 // over 8 claimed slots (8 keys and its own), and every other key of a dead
 // bucket counts itself, so the counts are exact.
 __global__ __launch_bounds__(256) void k_vt_build(const uint8_t* __restrict__ arena,
+                                                  const uint8_t* __restrict__ sum,
                                                   uint64_t n_pages, uint64_t lo, uint32_t shift,
                                                   uint64_t n_b, uint64_t* vt, uint64_t* ctr) {
   const int lane = lane_id();
@@ -326,7 +347,7 @@ __global__ __launch_bounds__(256) void k_vt_build(const uint8_t* __restrict__ ar
   for (uint64_t pi = 1 + (uint64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
        pi < n_pages; pi += nw) {
     const uint8_t* pg = arena + (pi << 10);
-    if (pg[kOffLevel] != 0 || pg64_b1(pg, 2) != 0) continue;  // a leaf (no leftmost)
+    if (!swept_leaf(arena, sum, pi)) continue;
     if (lane >= kLeafCardinality) continue;
     uint64_t k, v, b;
     uint32_t f, r;
@@ -352,10 +373,11 @@ __global__ __launch_bounds__(256) void k_vt_build(const uint8_t* __restrict__ ar
   }
 }
 
-void launch_vt_build(const uint8_t* arena, uint64_t n_pages, uint64_t lo, uint32_t shift,
-                     uint64_t n_buckets, uint64_t* vt, uint64_t* ctr, hipStream_t s) {
+void launch_vt_build(const uint8_t* arena, const uint8_t* sum, uint64_t n_pages, uint64_t lo,
+                     uint32_t shift, uint64_t n_buckets, uint64_t* vt, uint64_t* ctr,
+                     hipStream_t s) {
   if (n_pages <= 1 || !n_buckets) return;
-  hipLaunchKernelGGL(k_vt_build, dim3(2048), dim3(256), 0, s, arena, n_pages, lo, shift,
+  hipLaunchKernelGGL(k_vt_build, dim3(2048), dim3(256), 0, s, arena, sum, n_pages, lo, shift,
                      n_buckets, vt, ctr);
 }
 

@@ -730,8 +730,8 @@ int vt_build(shm_tree* t, hipStream_t s, bool want) {
   t->vt_bits = bits;
   HIP_OK(hipMemsetAsync(t->vt, 0, bytes, s));
   HIP_OK(hipMemsetAsync(t->vt_ctr, 0, 8 * dev::kVtCtrWords, s));
-  dev::launch_vt_build(t->arena, t->next_page, t->cfg.key_lo, t->cfg.key_bits - bits, 1ull << bits,
-                       t->vt, t->vt_ctr, s);
+  dev::launch_vt_build(t->arena, t->sum, t->next_page, t->cfg.key_lo, t->cfg.key_bits - bits,
+                       1ull << bits, t->vt, t->vt_ctr, s);
   // the counts into the host words (the drop rule reads them lazily)
   t->vt_seq = t->vt_seq + 1 ? t->vt_seq + 1 : 1;
   dev::launch_readback(t->h_pin_dev + kVtWord, reinterpret_cast<const uint32_t*>(t->vt_ctr), 6,
@@ -772,7 +772,7 @@ int refresh_dir(shm_tree* t, hipStream_t s) {
                        t->cfg.key_bits - bits, 1ull << bits, t->dir, t->dir_hint,
                        t->hint_ok ? 1 : 0, t->sum, t->d_err, s, pairs ? 1 : 0);
   if (pairs)
-    dev::launch_dir_pairs(t->arena, t->next_page, t->cfg.node_id, t->cfg.key_lo,
+    dev::launch_dir_pairs(t->arena, t->sum, t->next_page, t->cfg.node_id, t->cfg.key_lo,
                           t->cfg.key_bits - bits, 1ull << bits, t->dir, s);
   // the value form is only ever read from an exact directory
   if (pairs && t->dir_vals && t->dir_maint)
@@ -2516,6 +2516,50 @@ int shm_dump_image(shm_tree* t, void* host_buf, uint64_t cap,
   return SHM_OK;
 }
 
+// The leaves a host image reaches from its root, one byte per page: the
+// closure of the root under the child pointers of internal pages and the
+// sibling pointers of all pages (a page that a missing separator left hanging
+// on its left sibling alone is reached, as for every reader).  A pointer to
+// another node, outside the image or off a page boundary is not followed
+// (shm_check reports such an image); every page is visited once.
+static void image_leaves(const uint8_t* img, uint64_t bytes, uint64_t pages, uint64_t root_ptr,
+                         uint16_t node, std::vector<uint8_t>& leaf) {
+  leaf.assign(pages, 0);
+  std::vector<uint8_t> seen(pages, 0);
+  std::vector<uint64_t> todo;
+  auto u64_at = [&](uint64_t off) {
+    uint64_t v;
+    memcpy(&v, img + off, sizeof(v));
+    return v;
+  };
+  auto push = [&](uint64_t ga) {
+    const uint64_t off = ga_offset(ga);
+    if (ga == 0 || ga_node(ga) != node || (off & (kPageSize - 1)) || off < kPageSize ||
+        off + kPageSize > bytes)
+      return;
+    const uint64_t p = off / kPageSize;
+    if (seen[p]) return;
+    seen[p] = 1;
+    todo.push_back(p);
+  };
+  push(root_ptr);
+  while (!todo.empty()) {
+    const uint64_t at = todo.back() * kPageSize;
+    todo.pop_back();
+    push(u64_at(at + kOffSibling));
+    const uint64_t leftmost = u64_at(at + kOffLeftmost);
+    if (leftmost == 0) {
+      leaf[at / kPageSize] = img[at + kOffLevel] == 0;
+      continue;
+    }
+    push(leftmost);
+    int16_t last;
+    memcpy(&last, img + at + kOffLastIndex, sizeof(last));
+    const int n = last < 0 ? 0 : last >= kInternalCardinality ? kInternalCardinality : last + 1;
+    for (int j = 0; j < n; ++j) push(u64_at(at + kOffRecords + kInternalEntry * j + 8));
+  }
+}
+
 int shm_load_image(shm_tree* t, const void* host_buf, uint64_t bytes,
                    uint64_t root_ptr) {
   if (!t || !host_buf || bytes < 2 * kPageSize) return SHM_EINVAL;
@@ -2528,10 +2572,28 @@ int shm_load_image(shm_tree* t, const void* host_buf, uint64_t bytes,
   HIP_OK(hipMemcpy(t->arena, host_buf, bytes, hipMemcpyHostToDevice));
   // occupancy unknown for the loaded pages: whole-page reads until rewritten
   HIP_OK(hipMemset(t->leaf_hw, kLeafHwFull, t->cap_pages));
-  // leaf summaries from the loaded pages
+  // leaf summaries from the loaded pages: of the leaves the image reaches from
+  // its root and of no other page, so no tag of the tree before it survives
+  // and a page the image only carries along gets none (the page sweeps of the
+  // directory's and the table's builds read tagged pages alone)
   HIP_OK(hipMemset(t->sum, 0, t->cap_pages * kSumBytes));
-  dev::launch_sum_rebuild(t->arena, pages, t->sum, nullptr);
-  HIP_OK(hipDeviceSynchronize());
+  {
+    std::vector<uint8_t> leaf;
+    image_leaves(static_cast<const uint8_t*>(host_buf), bytes, pages, root_ptr, t->cfg.node_id, leaf);
+    uint8_t* d_leaf = nullptr;
+    if (hipMalloc((void**)&d_leaf, pages) != hipSuccess) {
+      (void)hipGetLastError();
+      return SHM_ENOMEM;
+    }
+    hipError_t e = hipMemcpy(d_leaf, leaf.data(), pages, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      dev::launch_sum_rebuild(t->arena, pages, d_leaf, t->sum, nullptr);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d_leaf);
+    HIP_OK(e);
+  }
   t->root = root_ptr;
   t->root_level = reinterpret_cast<const uint8_t*>(host_buf)[ro + kOffLevel];
   t->next_page = pages;

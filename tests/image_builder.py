@@ -285,3 +285,192 @@ def build_entry_states(seed=0, page_ver=1, node_id=0):
         "n_valid": int(ok.sum()), "n_torn": int((kind == TORN).sum()), "root_level": 2,
     }
     return img.reshape(-1), int(_ga(page[2][0], node_id)), info
+
+
+# ---- soil: pages the tree does not reach -------------------------------------------
+# slot kinds of soil_pages
+ABSENT, SHADOW, OUTSIDE, NULL = "absent", "shadow", "outside", "null"
+SOIL_KINDS = (ABSENT, SHADOW, DELETED, OUTSIDE, TORN, NULL)
+SOIL_XOR = 0x5011  # a soil entry's value is key ^ SOIL_XOR: never the tree's key ^ VALUE_XOR
+
+
+def soil_pages(n, keys_by_kind, seed, node_id=0, first_page=1, page_ver=1):
+    """n pages that look like current pages of a tree and are linked from
+    nowhere: what a page sweep over [1, next_page) meets below next_page after
+    a failed take, a shrinking reload or a load of such an image.
+
+    keys_by_kind maps a kind to its keys (a kind left out has none):
+      "absent"   valid entries (f == r, value != 0) of keys the tree never held
+      "shadow"   valid entries of keys the tree holds, with another value
+      "deleted"  valid entries of keys the tree holds as deleted slots
+      "outside"  valid entries of keys outside the tree's key range hint
+      "torn"     entries with a value whose f and r differ in the low nibble
+      "null"     entries with value 0
+    A valid or torn entry's value is key ^ SOIL_XOR.  With n >= 2 page 0 of the
+    soil looks internal: level 1, a leftmost pointer and (key, pointer) records
+    of the valid keys, pointing at the soil's leaves as if the soil were
+    appended at page `first_page`; read as a leaf its slots would hold valid
+    entries, and only its level and leftmost say it is none.  Every other page
+    is a leaf to a sweep: level 0, leftmost 0, front == rear version, sibling 0,
+    fences around its own keys, last_index -1 as the other builders write it.
+    The entries are dealt over the leaves in turn, into random slots.
+
+    Returns (pages, info): pages (n, 1024) uint8; info["slots"] = {"page" (the
+    index into pages), "slot", "key", "value", "kind"} of every leaf entry,
+    info[kind] the sorted keys of each kind, "leaf_pages" / "internal_pages"
+    the indices into pages."""
+    rng = np.random.default_rng([seed, 0x5011, n])
+    unknown = set(keys_by_kind) - set(SOIL_KINDS)
+    if unknown:
+        raise ValueError(f"unknown soil kinds {sorted(unknown)}")
+    pages = np.zeros((n, PAGE), dtype=np.uint8)
+    internal = [0] if n >= 2 else []
+    leaves = np.array([p for p in range(n) if p not in internal], dtype=np.int64)
+    kinds = [k for k in SOIL_KINDS if len(keys_by_kind.get(k, ()))]
+    key = np.concatenate([np.asarray(keys_by_kind[k], dtype=U64) for k in kinds] or
+                         [np.zeros(0, dtype=U64)])
+    kind = np.concatenate([np.full(len(keys_by_kind[k]), k) for k in kinds] or
+                          [np.zeros(0, dtype="<U8")])
+    if key.size > leaves.size * LEAF_SLOTS:
+        raise ValueError("more soil entries than slots")
+    if np.any(key == U64(0)) or np.any(key == U64(KEY_MAX)) or np.any(key == U64(SOIL_XOR)):
+        raise ValueError("a soil key a valid entry cannot hold")
+    o = rng.permutation(key.size)  # the kinds mixed over the pages
+    key, kind = key[o], kind[o]
+    pg = leaves[np.arange(key.size) % leaves.size] if key.size else np.zeros(0, dtype=np.int64)
+    slot = np.empty(key.size, dtype=np.int64)
+    for p in leaves:
+        mine = np.nonzero(pg == p)[0]
+        slot[mine] = rng.permutation(LEAF_SLOTS)[:mine.size]
+    value = np.where(kind == NULL, U64(0), key ^ U64(SOIL_XOR))
+    f = rng.integers(0, 16, key.size)
+    r = np.where(kind == TORN, (f + 1 + rng.integers(0, 14, key.size)) & 0xF, f)
+    assert np.all(((f ^ r) & 0xF != 0) == (kind == TORN))
+    _put_entries(pages, pg, slot, key, value, f, r)
+    pages[leaves, OFF_FRONT_VER] = page_ver
+    pages[leaves, OFF_LEAF_REAR] = page_ver
+    pages[leaves, OFF_LEVEL] = 0
+    pages[leaves, OFF_LAST_INDEX:OFF_LAST_INDEX + 2] = np.array([-1], dtype="<i2").view(np.uint8)
+    for p in leaves:
+        mine = key[pg == p]
+        lo, hi = (int(mine.min()), int(mine.max()) + 1) if mine.size else (64, 128)
+        _put64(pages, [p], OFF_LOWEST, [lo])
+        _put64(pages, [p], OFF_HIGHEST, [hi])
+    for p in internal:
+        valid = np.sort(key[(kind != TORN) & (kind != NULL)])[:INTERNAL_SLOTS - 1]
+        if valid.size == 0:
+            valid = np.array([64], dtype=U64)
+        pages[p, OFF_FRONT_VER] = page_ver
+        pages[p, OFF_INTERNAL_REAR] = page_ver
+        pages[p, OFF_LEVEL] = 1
+        pages[p, OFF_LAST_INDEX:OFF_LAST_INDEX + 2] = \
+            np.array([valid.size - 1], dtype="<i2").view(np.uint8)
+        _put64(pages, [p], OFF_LEFTMOST, _ga([first_page + int(leaves[0])], node_id))
+        _put64(pages, [p], OFF_LOWEST, [0])
+        _put64(pages, [p], OFF_HIGHEST, [KEY_MAX])
+        to = first_page + leaves[np.arange(valid.size) % leaves.size]
+        for j in range(valid.size):
+            _put64(pages, [p], OFF_RECORDS + INTERNAL_ENTRY * j, [valid[j]])
+            _put64(pages, [p], OFF_RECORDS + INTERNAL_ENTRY * j + 8, _ga([to[j]], node_id))
+    info = {"slots": {"page": pg, "slot": slot, "key": key, "value": value, "kind": kind},
+            "leaf_pages": leaves, "internal_pages": np.array(internal, dtype=np.int64)}
+    for k in SOIL_KINDS:
+        info[k] = np.sort(key[kind == k])
+    return pages, info
+
+
+def with_soil(img, pages):
+    """the image with the soil pages appended (the root pointer stays)"""
+    img = np.asarray(img, dtype=np.uint8).reshape(-1)
+    assert img.size % PAGE == 0
+    return np.concatenate([img, np.asarray(pages, dtype=np.uint8).reshape(-1)])
+
+
+def soil_sizes(n):
+    """(keys per valid kind, keys per torn / null kind) that fill the leaves
+    of n soil pages: at most 32 and 16, and 17 and 1 for a single leaf"""
+    slots = LEAF_SLOTS * max(n - 1, 1)
+    per_kind = min(32, (slots - 2) // 3)
+    return per_kind, min(16, (slots - 3 * per_kind) // 2)
+
+
+def soil_keys(info, per_kind=32, per_bad=16, hint=(0, 64)):
+    """Soil keys for an image of this module, by kind, from its info: shadow
+    keys are stored keys outside the hot leaf (every leaf of these images but
+    the hot one is thin against a bucket of the key-value table: a few keys
+    in a span of 2^55 and more), absent / torn / null keys lie 8, 40 and 48
+    above other stored keys (every key the builders write, valid or not, is a
+    multiple of 64 above a fence that is one), deleted keys come from
+    info["deleted"], and outside keys lie 56 above stored keys outside the key
+    range hint (lo, bits); none with the full range."""
+    k = np.asarray(info["keys"], dtype=U64)
+    if "hot_lo" in info:
+        k = k[(k < U64(info["hot_lo"])) | (k >= U64(info["hot_hi"]))]
+
+    def spread(a, m):
+        a = np.asarray(a, dtype=U64)
+        return a[np.unique(np.linspace(0, a.size - 1, min(m, a.size)).astype(np.int64))]
+
+    lo, bits = hint
+
+    def inside(a):
+        a = np.asarray(a, dtype=U64)
+        if bits >= 64:
+            return np.ones(a.size, dtype=bool)
+        return (a >= U64(lo)) & (a - U64(lo) < U64(1 << bits))
+
+    kin, kout = k[inside(k)], k[~inside(k)]
+    dele = np.asarray(info["deleted"], dtype=U64)
+    out = {SHADOW: spread(kin[0::3], per_kind), ABSENT: spread(kin[1::3], per_kind) + U64(8),
+           TORN: spread(kin[2::3], per_bad) + U64(40),
+           NULL: spread(kin[2::3], per_bad) + U64(48),
+           DELETED: spread(dele[inside(dele)], per_kind),
+           OUTSIDE: spread(kout, per_kind) + U64(56)}
+    return out
+
+
+# ---- what a page sweep takes, and what the tree reaches ------------------------------
+def sweep_leaf(pages):
+    """the sweepers' leaf test on (n, 1024) uint8 pages: level byte 0 and no
+    leftmost pointer"""
+    leftmost = np.ascontiguousarray(pages[:, OFF_LEFTMOST:OFF_LEFTMOST + 8]).view("<u8").ravel()
+    return (pages[:, OFF_LEVEL] == 0) & (leftmost == 0)
+
+
+def sweep_entries(pages):
+    """(page, slot, key, value) of every entry a sweep would take from the
+    pages: the valid entries (value != 0, f == r in the low nibble) of the
+    pages sweep_leaf accepts"""
+    rec = pages[:, OFF_RECORDS:OFF_RECORDS + LEAF_SLOTS * LEAF_ENTRY]
+    rec = rec.reshape(-1, LEAF_SLOTS, LEAF_ENTRY)
+    k = np.ascontiguousarray(rec[:, :, 1:9]).view("<u8").reshape(-1, LEAF_SLOTS)
+    v = np.ascontiguousarray(rec[:, :, 9:17]).view("<u8").reshape(-1, LEAF_SLOTS)
+    ok = (v != 0) & (((rec[:, :, 0] ^ rec[:, :, 17]) & 0xF) == 0) & sweep_leaf(pages)[:, None]
+    pg, sl = np.nonzero(ok)
+    return pg, sl, k[pg, sl], v[pg, sl]
+
+
+def reached_pages(img, root_ptr):
+    """Mask over the image's pages: the pages reached from the root through
+    the leftmost pointer and the records of internal pages and the sibling
+    pointer of every page (a page that hangs on its left sibling alone is
+    reached, as for every reader)."""
+    pg = np.asarray(img, dtype=np.uint8).reshape(-1, PAGE)
+
+    def f64(p, off):
+        return int(np.ascontiguousarray(pg[p, off:off + 8]).view("<u8")[0])
+
+    seen = np.zeros(pg.shape[0], dtype=bool)
+    todo = [int(root_ptr) >> 26]
+    while todo:
+        p = todo.pop()
+        if not 0 < p < pg.shape[0] or seen[p]:
+            continue
+        seen[p] = True
+        todo.append(f64(p, OFF_SIBLING) >> 26)
+        if f64(p, OFF_LEFTMOST):
+            todo.append(f64(p, OFF_LEFTMOST) >> 26)
+            last = int(np.ascontiguousarray(pg[p, OFF_LAST_INDEX:OFF_LAST_INDEX + 2]).view("<i2")[0])
+            for j in range(min(max(last + 1, 0), INTERNAL_SLOTS)):
+                todo.append(f64(p, OFF_RECORDS + INTERNAL_ENTRY * j + 8) >> 26)
+    return seen
