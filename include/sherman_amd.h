@@ -213,6 +213,11 @@ int shm_insert_batch_async(shm_tree *t, const uint64_t *keys, const uint64_t *va
  * SHM_EAGAIN with a single ticket outstanding: the chunk ids start over and
  * the chunk of that ticket must be applied under its old id first.  Apply it
  * and call again.
+ * An empty chunk (n == 0; keys / vals may be null) takes no chunk id and
+ * queues nothing: shm_insert_order returns SHM_OK with ticket 0, also while
+ * two tickets are outstanding, and shm_insert_apply of ticket 0 returns
+ * SHM_OK at any time and leaves the tree and the outstanding tickets as they
+ * are.  No chunk has id 0.
  * Errors are reported as for shm_insert_batch_async.  Tree::insert
  * (src/Tree.cpp:353-403) for a batch, as shm_insert_batch_async. */
 int shm_insert_order(shm_tree *t, const uint64_t *keys, const uint64_t *vals, uint64_t n,

@@ -796,6 +796,29 @@ class Tree:
         chunks are pending or when value is below the counter."""
         _check(_hooks().shm__seq_jump(self.h, {"chunk": 0, "scan": 1}[which], value), "seq_jump")
 
+    def order_read(self, ticket, n):
+        """Test hook (shm__order_read): the ordered chunk of an outstanding
+        insert_order ticket of n ops, as insert_apply will read it: (uk, uv,
+        dk, counts), numpy uint64 arrays (upsert keys ascending with their
+        values, delete keys ascending) and counts = (upserts, deletes).  Waits
+        for the ordering; the ticket stays outstanding.  Any other ticket
+        raises ShermanError(SHM_EINVAL)."""
+        import numpy as np
+        uk, uv, dk = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
+        c = (u64 * 2)()
+        _check(_hooks().shm__order_read(self.h, ticket, uk.ctypes.data_as(vp),
+                                        uv.ctypes.data_as(vp), dk.ctypes.data_as(vp), c),
+               "order_read")
+        nu, nd = int(c[0]), int(c[1])
+        return uk[:nu], uv[:nu], dk[:nd], (nu, nd)
+
+    def insert_batch_padded(self, keys, vals, stream=None):
+        """Test hook (shm__insert_batch_padded): a routed insert's received
+        slots queued as insert_batch_async of one chunk, KEY_MAX keys being
+        slot padding that is skipped."""
+        _check(_hooks().shm__insert_batch_padded(self.h, _ptr(keys), _ptr(vals), keys.numel(),
+                                                 _stream_ptr(stream)), "insert_batch_padded")
+
     def dir_verify(self):
         """Diagnostics (shm__dir_verify): every directory entry the walks
         trust checked against the tree as it is now."""
@@ -943,6 +966,9 @@ _HOOKS = [
     ("shm__vt_dump", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64)]),
     ("shm__get_forms", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     ("shm__seq_jump", ctypes.c_int, [vp, ctypes.c_int, u32]),
+    ("shm__order_read", ctypes.c_int, [vp, u32, vp, vp, vp, ctypes.POINTER(u64)]),
+    ("shm__order_limits", ctypes.c_int, [ctypes.POINTER(u64)]),
+    ("shm__insert_batch_padded", ctypes.c_int, [vp, vp, vp, u64, vp]),
 ]
 
 
@@ -956,6 +982,15 @@ def _hooks():
             raise AttributeError(f"{LIB_PATH} lacks the hook {name}")
         f.restype, f.argtypes = res, args
     return L
+
+
+def order_limits():
+    """Test hook (shm__order_limits; no GPU): the compiled constants that
+    decide the path an insert chunk's ordering takes (isort.hip)."""
+    out = (u64 * 6)()
+    _check(_hooks().shm__order_limits(out), "order_limits")
+    names = ("tile", "max_tiles", "uniq_cap", "sub_cap", "coarse", "fine")
+    return {k: int(v) for k, v in zip(names, out)}
 
 
 class LocalGroup:

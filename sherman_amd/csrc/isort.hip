@@ -227,8 +227,8 @@ __global__ __launch_bounds__(kIT) void k_tile_dedup(const uint64_t* __restrict__
 //      the sub-bucket's keys below its own (keys are unique after a.; the
 //      sub-bucket's keys are LDS broadcast reads for the lanes that share
 //      it), its value fetched from `vals` meanwhile into LDS at that place.
-//      A sub-bucket > 64 (skewed keys) sorts the whole bin with the LDS
-//      bitonic network instead (values then fetched in d.);
+//      A sub-bucket > kSubRankCap = 64 (skewed keys) sorts the whole bin
+//      with the LDS bitonic network instead (values then fetched in d.);
 //   d. each survivor's value classifies it as an upsert or a delete (value 0
 //      = kValueNull, Tree.cpp:881); local ranks by one block scan.
 // The bin's (upserts, deletes) give its place among the bins (bin_prefix),
@@ -237,6 +237,9 @@ __global__ __launch_bounds__(kIT) void k_tile_dedup(const uint64_t* __restrict__
 constexpr int kUniqSlots = 8192;  // LDS hash slots (96 KB with the op indices)
 constexpr int kUniqCap = 6144;    // ops per bin handled here (load <= 0.75)
 constexpr int kUniqPer = kUniqCap / kIT;
+// a fine sub-bucket of more distinct keys than this sends its whole bin to
+// the bitonic finish (step c.'s rank loop reads a sub-bucket's every key)
+constexpr int kSubRankCap = 64;
 
 
 // ---- bins over kUniqCap ops: the same result through global scratch ---------
@@ -585,7 +588,7 @@ __global__ __launch_bounds__(kIT) void k_bin_unique(uint64_t* __restrict__ keys1
   bstamp(1);
   // b. survivors placed by fine digit: sub-bucket base + the claim's rank
   const uint32_t hc = t < kFine ? hist[t] : 0u;
-  if (hc > 64) s_big = 1;
+  if (hc > (uint32_t)kSubRankCap) s_big = 1;
   uint32_t u;
   const uint32_t hex = block_scan(hc, wsum, &u);  // ends with a barrier
   if (t < kFine) hist[t] = hex;
@@ -720,6 +723,15 @@ void launch_bin_unique(uint64_t* keys1, uint32_t* pay1, const uint32_t* bins, ui
   hipLaunchKernelGGL(k_bin_unique, dim3(kCoarse), dim3(kIT), 0, s, keys1, pay1, bins, kr, vals,
                      lrank, lbw, kscr, iscr, uk, uv, dk, counts, err, S, gate, tag, stamps, tr,
                      ids);
+}
+
+void order_limits(uint64_t out[6]) {
+  out[0] = kIsortTile;
+  out[1] = kMaxTiles;
+  out[2] = kUniqCap;
+  out[3] = kSubRankCap;
+  out[4] = kCoarse;
+  out[5] = kFine;
 }
 
 }  // namespace dev

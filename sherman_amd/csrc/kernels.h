@@ -496,6 +496,10 @@ void launch_bin_unique(uint64_t* keys1, uint32_t* pay1, const uint32_t* bins, ui
                        uint64_t* counts, uint32_t* err, uint32_t* S, const uint32_t* gate,
                        uint32_t tag, uint64_t* stamps, const TileRuns& tr, uint32_t* ids,
                        hipStream_t s);
+// the constants that decide an ordering's path (shm__order_limits): tile
+// size, tiles in tile mode, ops of a bin sorted in LDS, keys of a fine
+// sub-bucket ranked in place, coarse bins, fine sub-buckets
+void order_limits(uint64_t out[6]);
 // out[i] = vals1[pos1[i]], found[i] = out[i] != 0
 void launch_unpartition(const uint64_t* vals1, const uint32_t* pos1, uint64_t n,
                         uint64_t* out, uint8_t* found, hipStream_t s);

@@ -539,6 +539,15 @@ __device__ __forceinline__ void delete_key(const UpperArgs& a, uint64_t k, uint3
   const int lane = lane_id();
   uint64_t ptr = a.root;
   if (a.dir) ptr = dir_start(a.dir, a.dir_lo, a.dir_shift, a.dir_n, a.node, k, ptr);
+  // The directory is as old as its last build, and the deletes run after the
+  // chunk's own splits: new keys clustered in one prefix may have put
+  // thousands of leaves between the entry's leaf and k's (more than
+  // kMaxRounds of them: kErrRounds, the delete dropped).  A walk that has
+  // moved right kDelDirMoves times from a directory start goes down from the
+  // root instead, whose levels the chunk has completed by now.
+  constexpr int kDelDirMoves = 16;
+  bool from_dir = ptr != a.root;
+  int moved = 0;
   bool locked = false;
   uint64_t lw = 0;
   int retries = 0;
@@ -546,6 +555,10 @@ __device__ __forceinline__ void delete_key(const UpperArgs& a, uint64_t k, uint3
     if (hop > kMaxRounds) {
       err |= kErrRounds;
       break;
+    }
+    if (from_dir && moved > kDelDirMoves) {
+      from_dir = false;
+      ptr = a.root;
     }
     if (!ptr_ok(ptr, a.node, a.arena_bytes)) {
       err |= kErrBadPtr;
@@ -565,6 +578,7 @@ __device__ __forceinline__ void delete_key(const UpperArgs& a, uint64_t k, uint3
     }
     if (k >= h0.highest && h0.sibling != 0) {
       ptr = h0.sibling;
+      ++moved;
       continue;
     }
     if (k < h0.lowest || k >= h0.highest) {
@@ -613,6 +627,7 @@ __device__ __forceinline__ void delete_key(const UpperArgs& a, uint64_t k, uint3
         __hip_atomic_store(a.locks + lw, a.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       locked = false;
       ptr = h.sibling;
+      ++moved;
       continue;
     }
     stage_page(lp, w);

@@ -1972,6 +1972,14 @@ int shm_insert_order(shm_tree* t, const uint64_t* keys, const uint64_t* vals, ui
                      void* stream, uint32_t* ticket) {
   if (!t || !ticket || (n && (!keys || !vals))) return SHM_EINVAL;
   if (n > t->nmax) return SHM_E2BIG;
+  if (n == 0) {
+    // An empty chunk takes no chunk id and queues nothing: ticket 0 (never a
+    // chunk id), which shm_insert_apply accepts as done.  The ordering of 0
+    // ops has no tile and no coarse pass, so k_bin_unique would read the bin
+    // table the last coarse pass left, with no values behind it.
+    *ticket = 0;
+    return SHM_OK;
+  }
   std::lock_guard<std::mutex> g(t->mu);
   if (t->n_pend >= 2) return SHM_EAGAIN;  // two op-buffer parities
   hipStream_t s = pick(stream);
@@ -2003,6 +2011,7 @@ int shm_insert_order(shm_tree* t, const uint64_t* keys, const uint64_t* vals, ui
 
 int shm_insert_apply(shm_tree* t, uint32_t ticket, void* stream) {
   if (!t) return SHM_EINVAL;
+  if (ticket == 0) return SHM_OK;  // an empty chunk (shm_insert_order, n == 0)
   std::lock_guard<std::mutex> g(t->mu);
   if (!t->n_pend || t->pend[0].tag != ticket) return SHM_EINVAL;  // oldest first
   const shm_tree::Pending pd = t->pend[0];
@@ -2402,6 +2411,43 @@ int shm__early_pages(shm_tree* t, uint64_t* out) {
   std::lock_guard<std::mutex> g(t->mu);
   HIP_OK(hipMemcpy(out, &t->ctl->ualloc[t->chunks & 1u][0], sizeof(uint64_t),
                    hipMemcpyDeviceToHost));
+  return SHM_OK;
+}
+
+// Test hook, not part of include/sherman_amd.h: the ordered chunk of an
+// outstanding shm_insert_order ticket, as its apply will read it.  Waits for
+// the ticket's ordering; counts_host[0..1] = {upserts, deletes}, then
+// uk_host / uv_host [0, upserts) and dk_host [0, deletes) (host buffers of the
+// chunk's n words each).  Changes no state: the ticket stays outstanding.
+// SHM_EINVAL for any ticket that is not outstanding.
+int shm__order_read(shm_tree* t, uint32_t ticket, uint64_t* uk_host, uint64_t* uv_host,
+                    uint64_t* dk_host, uint64_t* counts_host) {
+  if (!t || !uk_host || !uv_host || !dk_host || !counts_host) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  const shm_tree::Pending* pd = nullptr;
+  for (int i = 0; i < t->n_pend; ++i)
+    if (t->pend[i].tag == ticket) pd = &t->pend[i];
+  if (!pd) return SHM_EINVAL;
+  HIP_OK(hipEventSynchronize(pd->ev));
+  HIP_OK(hipMemcpy(counts_host, op_counts(t, ticket), 2 * sizeof(uint64_t),
+                   hipMemcpyDeviceToHost));
+  const uint64_t nu = counts_host[0], nd = counts_host[1];
+  if (nu > pd->n || nd > pd->n) return SHM_EIO;  // the buffers hold n words
+  if (nu) {
+    HIP_OK(hipMemcpy(uk_host, op_keys(t, ticket), nu * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(uv_host, op_vals(t, ticket), nu * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+  if (nd)
+    HIP_OK(hipMemcpy(dk_host, op_dels(t, ticket), nd * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return SHM_OK;
+}
+
+// Test hook, not part of include/sherman_amd.h: the compiled constants that
+// decide the path an ordering takes (isort.hip order_limits): out[0..5] =
+// kIsortTile, kMaxTiles, kUniqCap, kSubRankCap, kCoarse, kFine
+int shm__order_limits(uint64_t* out) {
+  if (!out) return SHM_EINVAL;
+  dev::order_limits(out);
   return SHM_OK;
 }
 

@@ -1033,7 +1033,10 @@ def test_insert_bin_overflow_reorders(lib_ok):
     """Clustered keys put > 6144 ops into one ordering bin: k_bin_unique sorts
     that bin on the device with its global-scratch LSD radix path
     (isort.hip big_bin_unique) with the same result; a bin of <= 6144
-    clustered keys takes the LDS bitonic fallback inside the bin."""
+    clustered keys takes the LDS bitonic fallback inside the bin.  (The paths
+    of these batches -- radix in two passes for 12000 and 16000 keys, the
+    bitonic network at width 8192 for 5000 -- are asserted on the host model
+    in tests/test_order_model.py.)"""
     t = shm.Tree(arena_bytes=64 << 20, max_batch=1 << 14)
     orc = OracleTree(64 << 20)
     rng = np.random.default_rng(11)
