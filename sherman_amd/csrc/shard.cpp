@@ -79,17 +79,7 @@
 #include "../../include/sherman_amd.h"
 #include "kernels.h"
 
-// library-internal (tree.cpp)
-extern "C" uint32_t* shm__error_word(shm_tree* t);
-extern "C" int shm__insert_batch_padded(shm_tree* t, const uint64_t* keys, const uint64_t* vals,
-                                        uint64_t n, void* stream);
-extern "C" int shm__route_bucket_insert(shm_tree* t, const uint64_t* keys, uint64_t n,
-                                        uint32_t num_shards, const uint64_t* splitters_host,
-                                        uint64_t* counts_out, uint64_t* keys_out,
-                                        uint32_t* perm_out, void* stream);
-extern "C" int shm__export_all(shm_tree* t, uint64_t** pairs_out, uint64_t* n_out, void* stream);
-extern "C" int shm__scan_u64(shm_tree* t, const uint64_t* in, uint64_t* out, uint64_t n,
-                             uint64_t* tot_dev, void* stream);
+#include "tree_hooks.h"
 
 namespace {
 

@@ -23,7 +23,7 @@ static int fails = 0;
   } while (0)
 
 // insert_begin / insert_apply, one chunk: the tag it gets and the clears its
-// apply makes (tree.cpp: new_mark(tag) == 1, the fan tag's low 29 bits zero)
+// apply makes (tree_insert.cpp: new_mark(tag) == 1, the fan tag's low 29 bits zero)
 struct ChunkModel {
   uint32_t chunks;
   bool marks = false, fan = false, epoch = false;

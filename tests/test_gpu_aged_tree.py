@@ -356,7 +356,7 @@ def test_a_real_stream_across_mark_periods(lib_ok, mode, leaf_dir):
     """600 chunks on one handle.  A leaf that got a new key in chunk T carries
     the byte mark new_mark(T) (kernels.h); chunk T + 255 has the same mark
     and brings that leaf overwrites only, so with the marks' clear missing
-    (tree.cpp insert_apply, new_mark(tag) == 1) the leaf is staged again:
+    (tree_insert.cpp insert_apply, new_mark(tag) == 1) the leaf is staged again:
     insert_staged above the twin's.  Contents against the oracle every 50
     chunks and at the end."""
     t0 = time.perf_counter()
@@ -433,7 +433,7 @@ def scan_seq_is(t, value):
 
 def test_b_scan_tags_recur_after_the_wrap(lib_ok):
     """launch_scan_u64_total's tile words carry scan_seq & 0xFFFF; scan_tag
-    (tree.cpp) zeroes them when the tag wraps and skips tag 0.  A three-tile
+    (tree_read.cpp) zeroes them when the tag wraps and skips tag 0.  A three-tile
     scan P leaves its tile sums under tag 0xFFFB; single-tile scans cross the
     wrap (they rewrite word 0 only); then a three-tile scan Q runs under the
     same 16-bit tag, 65,536 counter steps later.  With the clear missing,
@@ -631,7 +631,7 @@ def test_d_fan_tags_recur_after_2_pow_29_chunks(lib_ok):
 @pytest.mark.parametrize("mode", ["batch", "pipe"])
 def test_e_handle_crosses_the_end_of_the_chunk_counter(lib_ok, mode):
     """40 chunks from tag 2^32 - 19 on: the chunk after 2^32 - 1 is tag 1 of a
-    new epoch (tree.cpp epoch_reset: the handle drained, the lock table and
+    new epoch (tree_insert.cpp epoch_reset: the handle drained, the lock table and
     every tagged word zeroed, the mirrors reset).  Without it every lock word
     an old chunk touched stays above tag << 32 of the new tags (kErrLock
     after the spin bound) and gate, skip and the tagged words of the handle's

@@ -321,7 +321,7 @@ def test_insert_every_cycles_build_once(lib_ok):
 
 
 def test_upkeep_policy_idle_and_write_only_streams(lib_ok):
-    """The default policy (tree.cpp insert_apply): a chunk keeps the
+    """The default policy (tree_dir.cpp dir_chunk_begin): a chunk keeps the
     directory only when gets read it since the last chunk and recent upkeeps
     found work.  Update-only chunks between searches (C3's mix) stop the
     upkeep after kIdleUpkeeps idle ones; a chunk with no search before it

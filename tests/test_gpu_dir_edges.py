@@ -394,7 +394,7 @@ def _growth(form, table):
         assert np.array_equal(tg.counts(), np.full(tg.p.size, c))
     done = {c: 0 for c in tgs}
     # A write phase whose chunks stop adding pages is rebuilt in the pair form
-    # after kQuietChunks = 2 of them (tree.cpp want_pairs).  To stay in the
+    # after kQuietChunks = 2 of them (tree_dir.cpp want_pairs).  To stay in the
     # fingerprint form each of its chunks also splits one leaf that holds no
     # target, with a run of 40 keys behind the leaf's lowest fence.
     taken = concat([tg.page for tg in tgs.values()])

@@ -62,7 +62,7 @@ def test_c2_full_size_get_parity(lib_ok):
     v = torch.empty_like(q)
     f = torch.empty(b, dtype=torch.uint8, device="cuda")
     # the form the bench's timed steps walk: the read phase's pair-form
-    # directory (four searches without an insert, tree.cpp kReadPhase)
+    # directory (four searches without an insert, tree_dir.cpp kReadPhase)
     for _ in range(4):
         t.search_batch(q, v, f)
     t.profile(False, index_stats=True)
@@ -90,7 +90,7 @@ def test_c2_full_size_get_parity(lib_ok):
     assert torch.equal(f.bool(), ~miss)
     # split-heavy chunks of new keys at full size (key(i) for ids past 2^26,
     # value 2i), a get batch after each (the gets that make the chunks keep
-    # the directory: tree.cpp insert_apply's policy), then gets before any
+    # the directory: tree_dir.cpp dir_chunk_begin's policy), then gets before any
     # rebuild: the chunks kept the pair-form entries (dir_upkeep.h), so every
     # stored key is still answered exactly -- old, new and their moved slots
     # -- with no rebuild

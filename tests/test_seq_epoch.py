@@ -1,7 +1,7 @@
 """The sequence hook's place in the C-ABI and the host arithmetic behind the
 counters' periods; both run without a GPU.
 
-* shm__seq_jump (tree.cpp) is a test hook: the built library exports it,
+* shm__seq_jump (tree_insert.cpp) is a test hook: the built library exports it,
   include/sherman_amd.h does not declare it;
 * sherman_amd/csrc/seq_epoch.h (which clears a jump of a counter owes, the end
   of the chunk counter's epoch) against step-by-step models of the real

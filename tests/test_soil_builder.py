@@ -26,7 +26,7 @@ U64 = np.uint64
 
 # The table of a read phase's build over an arena of at most 1024 pages: the
 # directory has 2^(10 + 4) entries over the key range hint, the table half as
-# many buckets (tree.cpp dir_bits_for, vt_build).
+# many buckets (tree_dir.cpp dir_bits_for, vt_build).
 TABLE_BITS = 13
 HINTS = {"full": (0, 64), "narrow": (1 << 62, 63)}
 VALID_KINDS = (ib.ABSENT, ib.SHADOW, ib.DELETED)
