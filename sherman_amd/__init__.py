@@ -844,6 +844,24 @@ class Tree:
         return ent, {"lo": int(info[1]), "shift": int(info[2]),
                      "form": DIR_FORMS.get(int(info[3]) if info[0] else 0, str(info[3]))}
 
+    def side_dump(self, pages=None):
+        """Test hook (shm__side_dump): the side state of the first `pages`
+        arena pages (None: the pages in use): the leaf summary lines as a
+        (pages, 64) uint8 array, the occupancy bounds as a (pages,) uint8
+        array, and {"next_page", "cap_pages"}.  pages may reach past
+        next_page, up to the arena's pages."""
+        import numpy as np
+        info = (u64 * 2)()
+        _check(_hooks().shm__side_dump(self.h, None, None, 0, info), "side_dump")
+        n = int(info[0]) if pages is None else int(pages)
+        if n > info[1]:
+            raise ValueError("side_dump: more pages than the arena has")
+        lines = np.zeros((n, 64), dtype=np.uint8)
+        hw = np.zeros(n, dtype=np.uint8)
+        _check(_hooks().shm__side_dump(self.h, lines.ctypes.data_as(vp), hw.ctypes.data_as(vp),
+                                       n, info), "side_dump")
+        return lines, hw, {"next_page": int(info[0]), "cap_pages": int(info[1])}
+
     def vt_stats(self):
         """Test hook (shm__vt_stats): the key-value bucket table a read
         phase's gets read first: buckets, bytes, dead buckets, the stored keys
@@ -969,6 +987,9 @@ _HOOKS = [
     ("shm__order_read", ctypes.c_int, [vp, u32, vp, vp, vp, ctypes.POINTER(u64)]),
     ("shm__order_limits", ctypes.c_int, [ctypes.POINTER(u64)]),
     ("shm__insert_batch_padded", ctypes.c_int, [vp, vp, vp, u64, vp]),
+    ("shm__side_dump", ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
+    ("shm__check_image", ctypes.c_int, [vp, u64, u64, ctypes.c_uint16, ctypes.POINTER(u64),
+                                        ctypes.POINTER(ctypes.c_int)]),
 ]
 
 
@@ -991,6 +1012,20 @@ def order_limits():
     _check(_hooks().shm__order_limits(out), "order_limits")
     names = ("tile", "max_tiles", "uniq_cap", "sub_cap", "coarse", "fine")
     return {k: int(v) for k, v in zip(names, out)}
+
+
+def check_image(image, root_ptr, node=0):
+    """Test hook (shm__check_image; no GPU): the structural check behind
+    Tree.check() on a host image.  Returns (code, counts): the check's raw
+    code (0 = sound) and {"leaves", "internal", "keys"} as it counted them
+    (all 0 for a rejected image)."""
+    import numpy as np
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    counts, code = (u64 * 3)(), ctypes.c_int(0)
+    _check(_hooks().shm__check_image(image.ctypes.data_as(vp), image.nbytes,
+                                     int(root_ptr) & ((1 << 64) - 1), node, counts,
+                                     ctypes.byref(code)), "check_image")
+    return code.value, dict(leaves=counts[0], internal=counts[1], keys=counts[2])
 
 
 class LocalGroup:

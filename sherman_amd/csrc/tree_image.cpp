@@ -11,7 +11,14 @@
 namespace shm {
 namespace host __attribute__((visibility("hidden"))) {
 
-// host-side structural check of an image (same invariants as SURVEY App. A)
+// host-side structural check of an image (same invariants as SURVEY App. A,
+// and two the reference's check does not state: no key is valid in two slots
+// of one leaf, -15, since a get answers from the first; and every child
+// pointer of a level names a page the sibling walk of the level below
+// visits, -16, since a stale copy of a page can carry the right lowest fence
+// and level).  A page that hangs on its left sibling alone is visited, so the
+// B-link state a failed take leaves passes.  tests/test_check_image.py pins
+// every code.
 int check_image(const uint8_t* img, uint64_t bytes, uint64_t root, uint16_t node,
                 uint64_t* n_leaves, uint64_t* n_internal, uint64_t* n_keys) {
   auto rd64 = [&](uint64_t off) {
@@ -30,9 +37,13 @@ int check_image(const uint8_t* img, uint64_t bytes, uint64_t root, uint16_t node
   if (ro < 0) return -1;
   int top = img[ro + kOffLevel];
   uint64_t head = root;
+  // the children the level above named, then the pages this level's walk visits
+  std::vector<uint64_t> named, kids, visited;
   for (int lvl = top; lvl >= 0; --lvl) {
     uint64_t p = head, expect_low = 0, next_head = 0;
     uint64_t guard = 0;
+    kids.clear();
+    visited.clear();
     while (p) {
       if (++guard > bytes / kPageSize + 1) return -20;
       const int64_t o = page_off(p);
@@ -45,16 +56,20 @@ int check_image(const uint8_t* img, uint64_t bytes, uint64_t root, uint16_t node
       if (pg[kOffFrontVer] != pg[is_leaf ? kOffLeafRear : kOffInternalRear]) return -5;
       const uint64_t lo = rd64(o + kOffLowest), hi = rd64(o + kOffHighest);
       if (lo != expect_low || hi <= lo) return -6;
+      visited.push_back((uint64_t)o);
       if (is_leaf) {
         int c = 0;
+        uint64_t held[kLeafCardinality];
         for (int i = 0; i < kLeafCardinality; ++i) {
           const uint64_t e = o + kOffRecords + (uint64_t)kLeafEntry * i;
           if (rd64(e + 9) == kValueNull) continue;
           const uint64_t k = rd64(e + 1);
           if (k < lo || k >= hi) return -7;
-          ++c;
+          held[c++] = k;
         }
         if (c > kLeafCardinality - 1) return -8;
+        std::sort(held, held + c);
+        if (std::adjacent_find(held, held + c) != held + c) return -15;
         keys += (uint64_t)c;
         ++leaves;
       } else {
@@ -65,6 +80,7 @@ int check_image(const uint8_t* img, uint64_t bytes, uint64_t root, uint16_t node
         if (!next_head) next_head = leftmost;
         int64_t co = page_off(leftmost);
         if (co < 0 || rd64(co + kOffLowest) != lo) return -10;
+        kids.push_back((uint64_t)co);
         uint64_t prev = lo;
         for (int j = 0; j < cnt; ++j) {
           const uint64_t k = rd64(o + kOffRecords + 16ull * j);
@@ -74,6 +90,7 @@ int check_image(const uint8_t* img, uint64_t bytes, uint64_t root, uint16_t node
           co = page_off(c);
           if (co < 0 || rd64(co + kOffLowest) != k) return -12;
           if ((int)img[co + kOffLevel] != lvl - 1) return -13;
+          kids.push_back((uint64_t)co);
         }
         ++internals;
       }
@@ -81,6 +98,11 @@ int check_image(const uint8_t* img, uint64_t bytes, uint64_t root, uint16_t node
       p = rd64(o + kOffSibling);
     }
     if (expect_low != kKeyMax) return -14;
+    // the fences ascend along a walk, so it visits no page twice
+    std::sort(visited.begin(), visited.end());
+    for (const uint64_t c : named)
+      if (!std::binary_search(visited.begin(), visited.end(), c)) return -16;
+    named.swap(kids);
     head = next_head;
   }
   if (n_leaves) *n_leaves = leaves;
@@ -552,6 +574,37 @@ int shm_tree_set_key_range(shm_tree* t, uint64_t key_lo, uint32_t key_bits) {
   // builds the directory (its entry count from the new key_bits: dir_bits_for),
   // the level hints and the bucket table over the new range
   dir_invalidate(t, true, true);
+  return SHM_OK;
+}
+
+// test hook: check_image on host memory, its raw code in *code (0 = sound)
+// and counts3 = {leaves, internal pages, valid keys} of a sound image.  No
+// handle and no GPU, like shm__order_limits (tests/test_check_image.py).
+int shm__check_image(const void* img, uint64_t bytes, uint64_t root, uint16_t node,
+                     uint64_t* counts3, int* code) {
+  if (!img || !code) return SHM_EINVAL;
+  uint64_t c[3] = {0, 0, 0};
+  *code = check_image(static_cast<const uint8_t*>(img), bytes, root, node, c, c + 1, c + 2);
+  if (counts3) memcpy(counts3, c, sizeof(c));
+  return SHM_OK;
+}
+
+// test hook: the side state of the pages, for a host-side check that shares
+// no code with the kernels (tests/state_model.py), in the style of
+// shm__dir_dump.  info = {next_page, cap_pages}; with buffers given
+// (nullable: sizes only) the summary lines (kSumBytes each) and the
+// occupancy bytes of the first min(cap_pages, the arena's pages) pages: the
+// caller may ask past next_page.
+int shm__side_dump(shm_tree* t, void* sum_out, void* hw_out, uint64_t cap_pages, uint64_t* info) {
+  if (!t || !info) return SHM_EINVAL;
+  std::lock_guard<std::mutex> g(t->mu);
+  HIP_OK(hipDeviceSynchronize());
+  mirror(t);
+  info[0] = t->next_page;
+  info[1] = t->cap_pages;
+  const uint64_t n = std::min(cap_pages, t->cap_pages);
+  if (sum_out && n) HIP_OK(hipMemcpy(sum_out, t->sum, n * kSumBytes, hipMemcpyDeviceToHost));
+  if (hw_out && n) HIP_OK(hipMemcpy(hw_out, t->leaf_hw, n, hipMemcpyDeviceToHost));
   return SHM_OK;
 }
 

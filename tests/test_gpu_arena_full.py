@@ -46,6 +46,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import arena_model as am  # noqa: E402
 import get_paths  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+import state_model as sm  # noqa: E402
 import test_gpu_tall as tall  # noqa: E402
 import valtab_model  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
@@ -96,8 +97,10 @@ def truth(t, info, also):
     """T: the oracle over the dumped image (with free pages after it, for the
     ops applied to both later).  Its structural check passes, the GPU's own
     check and shape agree with it, and its dump and its search from the root
-    agree over every probe.  Returns T, its sorted contents, the probes."""
-    img, root = t.dump_image()
+    agree over every probe, and the side state of the pages is sound for the
+    image (tall.assert_side: the caller has read and reset the failed chunk's
+    error bits).  Returns T, its sorted contents, the probes."""
+    img, root, _, _ = tall.assert_side(t, "the dumped image")
     T = OracleTree(image=img, root_ptr=root, spare_bytes=ROOM)
     rc, shape = T.check()
     assert rc == 0, rc
@@ -294,6 +297,29 @@ def split_thin_leaves(info, n):
     return (pick[:, None] + U64(info["step"] // 64) * np.arange(1, 61, dtype=U64)[None, :]).ravel()
 
 
+def unsplit_leaf_keeps_its_side_state(t, info, new, side0):
+    """After the failed hot chunk: where the hot leaf's split did not fit (the
+    leaf still covers its range and holds none of the new keys), its summary
+    line and its occupancy bound are byte for byte those of before the chunk;
+    and every page the failed take lost (below next_page, reached from
+    nowhere) is untagged."""
+    lines0, hw0, _ = side0
+    img, root = t.dump_image()
+    lines, hw, si = t.side_dump()
+    pg = img.reshape(-1, PAGE)
+    p = info["hot_page"]
+    held = sm._slots(pg[p:p + 1])
+    stored = np.isin(new, held[0][0][held[1][0] != 0])
+    unsplit = not stored.any() and \
+        sm._f64(pg[p:p + 1], sm.OFF_HIGHEST)[0] == U64(info["hot_hi"]) and pg[p, sm.OFF_LEVEL] == 0
+    lost = np.nonzero(~sm.reached_pages(img, root)[1:])[0] + 1
+    print(f"hot leaf {'unsplit' if unsplit else 'split'}, pages lost to the take: {lost.tolist()}")
+    if unsplit:
+        assert np.array_equal(lines[p], lines0[p]) and hw[p] == hw0[p], \
+            (p, lines[p].tolist(), lines0[p].tolist(), int(hw[p]), int(hw0[p]))
+    assert not (lines[lost, sm.SUM_OFF_TAG] == sm.SUM_LEAF).any(), lost
+
+
 CASES_A = [(m, "middle") for m in tall.MODES] + [("default", "left"), ("default", "right")]
 
 
@@ -325,7 +351,9 @@ def test_exact_arena(lib_ok, monkeypatch, mode, path, spare):
         t.close()
         return
     assert shm._hooks().shm__upper_force(t.h, tall.MODES[mode]) == 0
+    side0 = t.side_dump()
     failed(lambda: t.insert_batch(dev(keys), dev(vals)), shm.SHM_ENOMEM)
+    unsplit_leaf_keeps_its_side_state(t, info, new, side0)
     outside = keys[(keys < U64(info["hot_lo"])) | (keys >= U64(info["hot_hi"]))]
     got = after_failure(t, info, before, after, (keys, vals), outside, monkeypatch,
                         same_again=True, more=lambda n: split_thin_leaves(info, n),

@@ -38,6 +38,7 @@ import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from scan_model import ScanModel  # noqa: E402
+import state_model  # noqa: E402
 
 U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
@@ -263,11 +264,28 @@ def spread_chunk(info, orc):
     return keys[o], vals[o]
 
 
+def assert_side(t, what, pages=None):
+    """The side state of the pages against the pages themselves
+    (tests/state_model.py): every leaf summary line and occupancy bound of
+    the first `pages` arena pages (None: the pages in use) is sound for the
+    dumped image; the structural check passes and no error bit is set.
+    Returns (image, root, lines, hw)."""
+    img, root = t.dump_image()
+    lines, hw, si = t.side_dump(pages)
+    assert si["next_page"] * ib.PAGE == img.size, (what, si, img.size)
+    bad = state_model.side_violations(img, root, lines, hw, si["next_page"])
+    assert bad == [], (what, len(bad), bad[:12])
+    t.check()
+    assert t.last_error()["bits"] == 0, (what, t.last_error())
+    return img, root, lines, hw
+
+
 def check_contents(t, orc, what):
     """The contents three ways: the numpy reader of the GPU's pages, the
-    oracle's own reader of them, and the GPU's gets of the oracle's keys."""
+    oracle's own reader of them, and the GPU's gets of the oracle's keys;
+    and the side state of the pages."""
     ok, ov = orc.dump()
-    img, root = t.dump_image()
+    img, root, _, _ = assert_side(t, what)
     dir_model.Image(img, root).assert_equals(ok, ov)
     again = OracleTree(image=img, root_ptr=root)
     rc, shape = again.check()

@@ -185,7 +185,8 @@ def every_reader(t, info, soil, what, monkeypatch, node_id=0, trees=True, keep=N
     assert_same(probe, *want, *gpu_search(t, probe), what + ", read phase")
     tall.check_reads(t, T, info, what + ", read phase")
     other_readers(t, kv, probe, soil_probes(soil), what + ", read phase")
-    img, root = t.dump_image()
+    # the side state after the read phase's builds: no unreached page is tagged
+    img, root, _, _ = tall.assert_side(t, what + ", read phase")
     if trees:
         size = dict(arena_bytes=img.nbytes + 4 * PAGE, max_batch=tall.MAX_BATCH, node_id=node_id)
         monkeypatch.setenv("SHM_VALTAB", "0")
@@ -194,6 +195,7 @@ def every_reader(t, info, soil, what, monkeypatch, node_id=0, trees=True, keep=N
         others += [(kind, shm.Tree(**size, **args)) for kind, args in tall.READ_TREES.items()]
         for name, other in others:
             other.load_image(img, root)
+            tall.assert_side(other, f"{what}, {name}, as loaded")
             assert_same(probe, *want, *gpu_search(other, probe), f"{what}, {name}, as loaded")
             for _ in range(6):  # its read phase
                 got = gpu_search(other, probe)
