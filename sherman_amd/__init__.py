@@ -966,8 +966,9 @@ def from_i64(x):
     return x & ((1 << 64) - 1)
 
 
-# library-internal test hooks (csrc/shard.cpp): an in-process group of P
-# shard handles on one GPU whose collectives are device copies
+# library-internal test hooks: an in-process group of P shard handles on one
+# GPU whose collectives are device copies (csrc/shard_xport.cpp), the forced
+# route (csrc/shard_hooks.cpp), and the tree's own (csrc/tree*.cpp)
 _HOOKS = [
     ("shm__local_group_create", ctypes.c_int, [u32, ctypes.POINTER(vp)]),
     ("shm__local_group_destroy", ctypes.c_int, [vp]),

@@ -345,10 +345,11 @@ int shm_range_query_slots(shm_tree* t, const uint64_t* from, const uint64_t* to,
 
 namespace {
 // shm_scan_batch and shm_rscan_batch: one argument check, one queueing, the
-// kernel by direction
-int scan_call(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n, uint64_t limit,
-              uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out, uint64_t* status_dev,
-              void* stream, bool descending) {
+// kernel by direction (static: inside extern "C" an unnamed namespace alone
+// leaves the name exported)
+static int scan_call(shm_tree* t, const uint64_t* from, const uint64_t* to, uint64_t n,
+                     uint64_t limit, uint64_t* keys_out, uint64_t* vals_out, uint64_t* counts_out,
+                     uint64_t* status_dev, void* stream, bool descending) {
   // the arguments first: a rejected call uses neither the handle nor the GPU
   if (limit == 0 || limit >= (1ull << 31)) return SHM_EINVAL;
   if (n && (!from || !keys_out || !vals_out || !counts_out)) return SHM_EINVAL;

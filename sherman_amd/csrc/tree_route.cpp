@@ -11,9 +11,10 @@
 extern "C" {
 
 namespace {
-int route_bucket(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
-                 const uint64_t* splitters, uint64_t* counts_out, uint64_t* keys_out,
-                 uint32_t* perm_out, void* stream, bool reject_keymax, int mode = 0) {
+// static: inside extern "C" an unnamed namespace alone leaves the name exported
+static int route_bucket(shm_tree* t, const uint64_t* keys, uint64_t n, uint32_t num_shards,
+                        const uint64_t* splitters, uint64_t* counts_out, uint64_t* keys_out,
+                        uint32_t* perm_out, void* stream, bool reject_keymax, int mode = 0) {
   if (!t || num_shards == 0 || num_shards > 64 || !counts_out) return SHM_EINVAL;
   if (n && (!keys || !keys_out || !perm_out)) return SHM_EINVAL;
   // ascending (repeats make empty shards), none kKeyMax: checked on the host
