@@ -33,6 +33,9 @@
  *                       (no reference counterpart beyond Tree::range_query's
  *                        traversal; the reference never frees a page,
  *                        include/LocalAllocator.h:45-47)
+ *   shm_rank_batch / shm_count_batch / shm_select_batch
+ *                       (no reference counterpart beyond Tree::range_query's
+ *                        traversal and validity rule: order statistics)
  *   shm_stats           Tree::print_and_check_tree / index_cache_statistics
  *                                                         include/Tree.h:56, 62; src/Tree.cpp:151-203
  *   shm_dump_image / shm_load_image
@@ -424,6 +427,66 @@ int shm_export(shm_tree *t, uint64_t lo, uint64_t hi, uint64_t *keys_out,
  * shm_bulk_load's own input check still runs on the exported run (about a
  * fifth of a load): a cross-check of the export. */
 int shm_compact(shm_tree *t, uint32_t leaf_fill, uint32_t internal_fill, void *stream);
+/* Order statistics: where a key stands in the key order, which pair stands at
+ * a position, and how many pairs a range holds (offset paging, quantiles,
+ * histograms, selectivity before a scan, the splitters of a first load).  No
+ * reference counterpart beyond Tree::range_query's traversal and validity
+ * rule (src/Tree.cpp:461-540, include/Tree.h:53-54: value != kValueNull, front
+ * == rear entry version); a torn entry is not counted.
+ *
+ *   shm_rank_batch:   ranks_out[i] = the number of valid pairs with key <
+ *     keys[i].  It counts exactly what shm_export(0, keys[i] - 1) counts
+ *     (0 for keys[i] == 0); for keys[i] == kKeyMax it is the total, since no
+ *     stored key equals kKeyMax.
+ *   shm_count_batch:  counts_out[i] = the number of valid pairs with from[i]
+ *     <= key <= to[i], i.e. rank(to[i] + 1) - rank(from[i]) with to[i] ==
+ *     kKeyMax meaning the total; from[i] > to[i] and from[i] == kKeyMax give
+ *     0.  It equals shm_range_query's counts on the same ranges, at a cost
+ *     that does not grow with the ranges.
+ *   shm_select_batch: the pair at position ranks[i] (from 0) of the key
+ *     order, i.e. element ranks[i] of shm_export(0, kKeyMax): keys_out[i],
+ *     vals_out[i], found_out[i] = 1; for ranks[i] >= the total kKeyMax, 0 and
+ *     0.  Each of the three outputs may be NULL, not all three.
+ *
+ * All pointers are DEVICE pointers; any n (not bounded by cfg.max_batch);
+ * n == 0 launches nothing and builds nothing.  The calls answer from an order
+ * index kept on the handle: the leaves of the whole tree in key order with the
+ * running count of their valid pairs (the whole-tree count pass of shm_export,
+ * kept, about 26 B per leaf) and sampled search levels over it, so a query is
+ * one search of the index and one leaf read.  Every call that can change the
+ * stored pairs or the pages (the inserts, shm_insert_apply, shm_mixed_batch
+ * with inserts, shm_del_batch, shm_bulk_load, shm_compact, a rebalance,
+ * shm_load_image) makes the index stale as it is issued; the next of these
+ * three calls rebuilds it first, and that call is synchronising like
+ * shm_export (it sees everything queued before it on any stream).  While the
+ * index is valid a call queues one kernel on `stream` and returns without a
+ * host wait.  Ordered like shm_scan_batch (exclusive); read-only: the tree,
+ * the leaf directory, the bucket table and shm_stats stay as they were.
+ * status_dev (device, 2 words, nullable): as shm_scan_batch's, the call ORs
+ * its device error bits into status_dev[1] and leaves status_dev[0] alone.
+ * SHM_EINVAL: a null handle, a null required array with n > 0 (before the
+ * handle is used), or an outstanding shm_insert_order ticket (its chunk is
+ * ordered but not applied); SHM_ENOMEM: the index could not be allocated (the
+ * handle stays usable); SHM_EIO with the error bits: a bad pointer, a walk
+ * past its bound, or an index that does not match the pages. */
+int shm_rank_batch(shm_tree *t, const uint64_t *keys, uint64_t n,
+                   uint64_t *ranks_out, uint64_t *status_dev, void *stream);
+int shm_count_batch(shm_tree *t, const uint64_t *from, const uint64_t *to,
+                    uint64_t n, uint64_t *counts_out, uint64_t *status_dev,
+                    void *stream);
+int shm_select_batch(shm_tree *t, const uint64_t *ranks, uint64_t n,
+                     uint64_t *keys_out, uint64_t *vals_out,
+                     uint8_t *found_out, uint64_t *status_dev, void *stream);
+/* The order index as it stands (host only; it builds nothing): `builds` tells
+ * a call that found the index valid from one that rebuilt it. */
+typedef struct shm_order_stats_t {
+  uint64_t units;         /* leaf units of the last build (0: never built) */
+  uint64_t pairs;         /* valid pairs it counted */
+  uint64_t bytes;         /* the index's device allocation */
+  uint64_t builds;        /* builds so far */
+  double last_build_ms;   /* host time of the last build, -1 before the first */
+} shm_order_stats_t;
+int shm_order_stats(shm_tree *t, shm_order_stats_t *out);
 /* Change the key range hint (cfg.key_lo / cfg.key_bits) of a live handle:
  * afterwards the handle behaves as one created with that hint.  The hint
  * steers the get ordering, the leaf directory and the bucket table only; keys

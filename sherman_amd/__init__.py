@@ -100,6 +100,11 @@ class ShmDirStats(ctypes.Structure):
                 ("maintained", u32), ("exact", u32)]
 
 
+class ShmOrderStats(ctypes.Structure):
+    _fields_ = [("units", u64), ("pairs", u64), ("bytes", u64), ("builds", u64),
+                ("last_build_ms", ctypes.c_double)]
+
+
 DIR_FORMS = {0: "none", 1: "fingerprints", 2: "pairs"}
 
 
@@ -148,6 +153,10 @@ _SIGNATURES = [
     ("shm_range_query_slots", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp]),
     ("shm_scan_batch", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp]),
     ("shm_rscan_batch", ctypes.c_int, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp]),
+    ("shm_rank_batch", ctypes.c_int, [vp, vp, u64, vp, vp, vp]),
+    ("shm_count_batch", ctypes.c_int, [vp, vp, vp, u64, vp, vp, vp]),
+    ("shm_select_batch", ctypes.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),
+    ("shm_order_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmOrderStats)]),
     ("shm_stats", ctypes.c_int, [vp, ctypes.POINTER(ShmStats)]),
     ("shm_dump_image", ctypes.c_int, [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     ("shm_load_image", ctypes.c_int, [vp, vp, u64, u64]),
@@ -681,6 +690,85 @@ class Tree:
         v = torch.zeros(n, dtype=torch.int64, device=keys.device)
         c, k, v = self.rscan_batch(keys, 1, stream=stream, keys=k, vals=v).result()
         return c != 0, k.view(-1), v.view(-1)
+
+    # -- order statistics ------------------------------------------------------
+    def rank_batch(self, keys, stream=None, out=None, status=None):
+        """The number of valid pairs below each key (shm_rank_batch): an int64
+        device tensor of n holding the u64 bits, what count(0, keys[i] - 1)
+        returns; KEY_MAX gives the total.  Answered from the order index: the
+        first call after a change of the tree rebuilds it and waits, later
+        ones queue one kernel on `stream` without a host wait.  out may be
+        passed in; status (2 device words, zeroed by the caller) gets the
+        device error bits ORed into status[1]."""
+        import torch
+        n = keys.numel()
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=keys.device)
+        assert out.numel() >= n
+        _check(lib().shm_rank_batch(self.h, _ptr(keys), n, _ptr(out), _ptr(status),
+                                    _stream_ptr(stream)), "rank_batch")
+        return out[:n]
+
+    def count_batch(self, lo, hi, stream=None, out=None, status=None):
+        """The number of valid pairs with lo[i] <= key <= hi[i]
+        (shm_count_batch): an int64 device tensor of n, range_query's counts
+        at a cost that does not grow with the ranges; lo > hi gives 0.
+        Queueing, out and status as in rank_batch."""
+        import torch
+        n = lo.numel()
+        assert hi.numel() == n
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=lo.device)
+        assert out.numel() >= n
+        _check(lib().shm_count_batch(self.h, _ptr(lo), _ptr(hi), n, _ptr(out), _ptr(status),
+                                     _stream_ptr(stream)), "count_batch")
+        return out[:n]
+
+    def select_batch(self, ranks, stream=None, keys=None, vals=None, found=None, status=None):
+        """The pair at each position of the key order, from 0
+        (shm_select_batch): (keys, vals, found), element ranks[i] of export();
+        past the end found is 0, the key KEY_MAX and the value 0.  Queueing
+        and status as in rank_batch; keys / vals (int64) and found (uint8)
+        may be passed in."""
+        import torch
+        n = ranks.numel()
+        dev = ranks.device
+        if keys is None:
+            keys = torch.empty(n, dtype=torch.int64, device=dev)
+        if vals is None:
+            vals = torch.empty(n, dtype=torch.int64, device=dev)
+        if found is None:
+            found = torch.empty(n, dtype=torch.uint8, device=dev)
+        assert keys.numel() >= n and vals.numel() >= n and found.numel() >= n
+        _check(lib().shm_select_batch(self.h, _ptr(ranks), n, _ptr(keys), _ptr(vals), _ptr(found),
+                                      _ptr(status), _stream_ptr(stream)), "select_batch")
+        return keys[:n], vals[:n], found[:n]
+
+    def order_stats(self):
+        """The order index as it stands (shm_order_stats; host only, builds
+        nothing): units, pairs, bytes, builds, last_build_ms."""
+        st = ShmOrderStats()
+        _check(lib().shm_order_stats(self.h, ctypes.byref(st)), "order_stats")
+        return {f: getattr(st, f) for f, _ in ShmOrderStats._fields_}
+
+    def quantile_keys(self, parts, stream=None):
+        """The keys at positions floor(p * N / parts) for p = 1 .. parts - 1
+        of the N stored pairs, the cuts of shm_rebalance_plan, by one select
+        batch: an int64 device tensor of parts - 1 keys, empty when
+        N < parts.  Waits for the result."""
+        import torch
+        dev = f"cuda:{self.device}"
+        top = torch.tensor([to_i64(KEY_MAX)], dtype=torch.int64, device=dev)
+        rank = self.rank_batch(top, stream)
+        self.synchronize()
+        total = from_i64(int(rank.item()))
+        if parts < 2 or total < parts:
+            return torch.empty(0, dtype=torch.int64, device=dev)
+        pos = torch.tensor([p * total // parts for p in range(1, parts)], dtype=torch.int64,
+                           device=dev)
+        keys, _, _ = self.select_batch(pos, stream)
+        self.synchronize()
+        return keys
 
     # -- reference single-op API (Tree.h:47-54) -------------------------------
     def _dev(self, name, n):

@@ -15,6 +15,7 @@
 //   void clear_statistics()                     clear_statistics()
 //   (new) the tree of a sorted run, one pass    bulk_load(keys, vals, n[, leaf_fill, internal_fill])
 //   (new) every pair of a range, in key order   export_sorted(keys, vals, cap[, lo, hi]), count([lo, hi])
+//   (new) order statistics                      rank(k), count_range(from, to), select(r, key, val)
 //   (new) the tree rebuilt from its own pairs   compact([leaf_fill, internal_fill])
 //   (new) the key range hint of a live tree    set_key_range(key_lo, key_bits)
 //   (new) batched forms on device pointers      search_batch / insert_batch / mixed_batch
@@ -209,6 +210,38 @@ class Tree {
   }
   // the number of valid pairs with lo <= key <= hi (shm_export's count pass)
   uint64_t count(Key lo = 0, Key hi = ~0ull) { return export_sorted(nullptr, nullptr, 0, lo, hi); }
+  // Order statistics (shm_rank_batch / shm_count_batch / shm_select_batch as
+  // batches of one; the first after a change of the tree rebuilds the order
+  // index).  rank: the valid pairs with key < k, i.e. count(0, k - 1);
+  // kKeyMax gives the total.
+  uint64_t rank(const Key& k) {
+    stage(k, nullptr);
+    check(shm_rank_batch(t_, d_keys_, 1, d_vals_, nullptr, nullptr), "rank");
+    return fetch(d_vals_, "rank copy-back");
+  }
+  // the valid pairs with from <= key <= to, what count(from, to) returns,
+  // without reading the leaves between the two ends
+  uint64_t count_range(const Key& from, const Key& to) {
+    uint64_t h[2] = {from, to};
+    if (hipMemcpy(d_keys_, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess)
+      throw Error(SHM_EIO, "count stage");
+    check(shm_count_batch(t_, d_keys_, d_keys_ + 1, 1, d_vals_, nullptr, nullptr), "count_range");
+    return fetch(d_vals_, "count copy-back");
+  }
+  // the pair at position r (from 0) of the key order, element r of
+  // export_sorted: false when r is not below the number of stored pairs
+  bool select(uint64_t r, Key& key_out, Value& val_out) {
+    stage(r, nullptr);
+    check(shm_select_batch(t_, d_keys_, 1, d_vals_, d_vals_ + 1, d_found_, nullptr, nullptr),
+          "select");
+    uint8_t f = 0;
+    if (hipMemcpy(&f, d_found_, 1, hipMemcpyDeviceToHost) != hipSuccess)
+      throw Error(SHM_EIO, "select copy-back");
+    if (!f) return false;
+    key_out = fetch(d_vals_, "select copy-back");
+    val_out = fetch(d_vals_ + 1, "select copy-back");
+    return true;
+  }
   // Rebuild the tree from its own valid pairs (shm_compact): the shape of
   // bulk_load(count(), leaf_fill, internal_fill), the pages deletes left behind
   // free again.  False: rejected before anything was written (SHM_EINVAL: fills
@@ -326,6 +359,12 @@ class Tree {
       throw Error(SHM_EIO, "stage key");
     if (v && hipMemcpy(d_vals_, v, sizeof(*v), hipMemcpyHostToDevice) != hipSuccess)
       throw Error(SHM_EIO, "stage value");
+  }
+  // one result word back from the device (after the call that wrote it)
+  uint64_t fetch(const uint64_t* d, const char* what) {
+    uint64_t v = 0;
+    if (hipMemcpy(&v, d, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) throw Error(SHM_EIO, what);
+    return v;
   }
   void release() {
     if (d_keys_) (void)hipFree(d_keys_);

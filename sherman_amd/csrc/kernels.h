@@ -765,6 +765,46 @@ uint64_t export_scan_tiles(uint64_t n);
 void launch_export_scan(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* bsum,
                         uint64_t* tot, const uint32_t* err, hipStream_t s);
 
+// ---- order statistics (order.hip) ------------------------------------------------
+// The order index: the whole tree's leaf units in key order (page, bound, and
+// off = the exclusive scan of their valid-pair counts with the total at
+// off[units]: the last export count pass's lists, copied), and over bound[]
+// and over off[1 ..] a pyramid of sampled levels.  Level 0 is the array
+// itself, level j + 1 holds the last word of every kOrdFan words of level j
+// (a block's largest), every level is padded to whole blocks with ~0, and the
+// top level is one block.  "The first word above x" is then one 128 B line per
+// level: the block found on the level above, one compare per lane.
+constexpr int kOrdFan = 16;     // words per block = lanes per query
+constexpr int kOrdLevels = 8;   // 16^8 units: more than any arena holds pages
+struct OrderArgs {
+  const uint8_t* arena;
+  uint64_t arena_bytes;
+  uint16_t node;
+  const uint8_t* leaf_hw;    // per-page occupancy bound (nullable), as in RangeArgs
+  uint32_t* err;
+  uint64_t* status;          // nullable: error bits ORed into status[1]
+  const uint64_t* page;      // the units
+  const uint64_t* bound;
+  const uint64_t* off;       // units + 1 words
+  const uint64_t* blv[kOrdLevels];  // blv[0] = bound
+  const uint64_t* olv[kOrdLevels];  // olv[0] = off + 1
+  uint64_t nblk[kOrdLevels];        // blocks of level j (both pyramids)
+  uint32_t nlev;
+  uint64_t units, total;
+  uint64_t max_pages;        // allocated pages at the build: bounds every chain walk
+  const uint64_t* in0;       // rank: keys; count: from; select: ranks
+  const uint64_t* in1;       // count: to
+  uint64_t n;
+  uint64_t* out0;            // rank: ranks; count: counts; select: keys (nullable)
+  uint64_t* out1;            // select: values (nullable)
+  uint8_t* found;            // select (nullable)
+};
+void launch_order_rank(const OrderArgs& a, hipStream_t s);
+void launch_order_count(const OrderArgs& a, hipStream_t s);
+void launch_order_select(const OrderArgs& a, hipStream_t s);
+// out[i] = in[min(kOrdFan i + kOrdFan - 1, n_in - 1)] for i < ceil(n_in / kOrdFan)
+void launch_order_sample(const uint64_t* in, uint64_t n_in, uint64_t* out, hipStream_t s);
+
 // ---- host read-backs (range.hip) ------------------------------------------------
 // dst[i] = src[i] for i < nw (<= 256, dst in mapped host memory), then a
 // system-scope release store of seq to *flag; clear: src[i] is exchanged

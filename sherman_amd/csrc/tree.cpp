@@ -256,7 +256,7 @@ void free_all(shm_tree* t) {
   F(t->ka); F(t->kb); F(t->ia); F(t->ib); F(t->ic); F(t->kc); F(t->id); F(t->part_mx); F(t->part_mt);
   F(t->uk); F(t->uv); F(t->dk); F(t->pages); F(t->seg_lb); F(t->bsum64);
   F(t->seg_start); F(t->seg_end); F(t->seg_page); F(t->seg_T); F(t->seg_P); F(t->seg_np);
-  F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->bulk_low); F(t->ex_ws); F(t->oslot); F(t->pnew);
+  F(t->seg_ver); F(t->leaf_hw); F(t->sum); F(t->bulk_low); F(t->ex_ws); F(t->oidx.ws); F(t->oslot); F(t->pnew);
   F(t->ctl); F(t->leaf_rd);
   for (int i = 0; i < 2; ++i) { F(t->sep_key[i]); F(t->sep_ptr[i]); F(t->ipage[i]); }
   F(t->h_end); F(t->h_T); F(t->h_P); F(t->h_ver); F(t->h_lk);

@@ -183,6 +183,7 @@ int shm_load_image(shm_tree* t, const void* host_buf, uint64_t bytes,
   const uint64_t ro = ga_offset(root_ptr);
   if (ro < kPageSize || ro + kPageSize > bytes) return SHM_EINVAL;
   HIP_OK(hipDeviceSynchronize());
+  ++t->ord_gen;  // the pages change: the order index is of the tree before
   HIP_OK(hipMemcpy(t->arena, host_buf, bytes, hipMemcpyHostToDevice));
   // occupancy unknown for the loaded pages: whole-page reads until rewritten
   HIP_OK(hipMemset(t->leaf_hw, kLeafHwFull, t->cap_pages));
@@ -283,6 +284,7 @@ static int bulk_load_locked(shm_tree* t, const uint64_t* keys, const uint64_t* v
   const uint64_t old_next = t->next_page;
   const uint64_t new_next = pl.pages + 1;
   const uint16_t node = t->cfg.node_id;
+  ++t->ord_gen;  // the pages change from here on: the order index is of the tree before
   // level l < root_level starts at page 2 + the pages of the levels below;
   // the root is page 1, as at create
   dev::BulkLeafArgs la{};
@@ -441,6 +443,26 @@ static int export_count(shm_tree* t, hipStream_t s, uint64_t lo, uint64_t hi, ui
   *n_out = total;
   return SHM_OK;
 }
+
+}  // extern "C"
+
+namespace shm {
+namespace host __attribute__((visibility("hidden"))) {
+int order_count(shm_tree* t, hipStream_t s, const uint64_t** page, const uint64_t** bound,
+                const uint64_t** off, const uint64_t** total_dev, uint64_t* total) {
+  if (const int rc = export_count(t, s, 0, kKeyMax, total)) return rc;
+  if (t->ex_units == 0) return SHM_EIO;  // the root alone is a unit: not a tree
+  const uint64_t cap = t->ex_cap;
+  *page = t->ex_ws + (uint64_t)t->ex_cur * cap;
+  *bound = t->ex_ws + (2 + (uint64_t)t->ex_cur) * cap;
+  *off = t->ex_ws + 5 * cap;
+  *total_dev = t->d_counts + 12;  // export_count's {total, error word}
+  return SHM_OK;
+}
+}  // namespace host
+}  // namespace shm
+
+extern "C" {
 
 // the pairs of the last export_count (lo, hi as there; total = its count)
 static int export_write(shm_tree* t, hipStream_t s, uint64_t lo, uint64_t hi, uint64_t* keys,

@@ -285,6 +285,10 @@ int insert_begin(shm_tree* t, hipStream_t s, const uint64_t* keys, const uint64_
 
 // steps 2-5 once the device state may change (the leaf directory current)
 int insert_finish(shm_tree* t, hipStream_t s, uint64_t n, uint32_t tag, shm_tree::ProfRec& pr) {
+  // every insert chunk passes here (shm_insert_batch and _async, shm_del_batch
+  // through them, shm_insert_apply, shm_mixed_batch, the padded hook): the
+  // order index is of the tree before it, whatever the chunk's status
+  ++t->ord_gen;
   if (use_leaf_dir(t)) {
     const int rc = refresh_dir(t, s);
     if (rc) return rc;

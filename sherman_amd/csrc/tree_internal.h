@@ -83,6 +83,25 @@ struct shm_tree {
   // the last count pass's leaf list (export_count -> export_write)
   int ex_cur = 0;
   uint64_t ex_units = 0;
+  // The order index (order.hip; tree_order.cpp): the last whole-tree count
+  // pass's leaf units (page, bound, off) and the sampled levels over bound and
+  // off, in one allocation of its own (the next export overwrites ex_ws);
+  // grown on demand, never shrunk.  It is of the tree as it was when ord_gen
+  // stood at oidx.gen: every host-side issue of work that can change the
+  // stored pairs or the pages bumps ord_gen (insert_finish, bulk_load_locked,
+  // shm_load_image), and a call that needs the index rebuilds it first when
+  // the two differ
+  uint64_t ord_gen = 0;
+  SHM_GROUP Oidx {
+    uint64_t* ws = nullptr;
+    uint64_t cap_words = 0;
+    bool valid = false;
+    uint64_t gen = 0;
+    uint64_t units = 0, total = 0;
+    uint64_t max_pages = 0;  // next_page at the build
+    uint64_t builds = 0;
+    double last_ms = -1.0;
+  } oidx;
   // upsert staging verdicts: per op the slot it overwrites (k_locate), per
   // page the last chunk tag that brought it a new key
   uint32_t* oslot = nullptr;
@@ -417,6 +436,14 @@ int dir_chunk_upkeep(shm_tree* t, hipStream_t s, const dev::UpperArgs& u, uint64
 uint64_t* op_counts(shm_tree* t, uint32_t tag);
 int insert_chunk(shm_tree* t, hipStream_t s, const uint64_t* keys, const uint64_t* vals,
                  uint64_t n, bool skip_pad = false);
+
+// ---- tree_image.cpp ------------------------------------------------------
+// the whole tree's count pass for the order index (export_count(0, kKeyMax)):
+// on success the leaf units stand in the export workspace, *page / *bound /
+// *off name their lists (units words each), *total_dev the device word that
+// holds the total, and t->ex_units / *total are their counts.  Synchronising
+int order_count(shm_tree* t, hipStream_t s, const uint64_t** page, const uint64_t** bound,
+                const uint64_t** off, const uint64_t** total_dev, uint64_t* total);
 
 // ---- tree_prof.cpp -------------------------------------------------------
 int prof_begin(shm_tree* t, hipStream_t s, int kind, uint64_t n, int ne, shm_tree::ProfRec& r);
