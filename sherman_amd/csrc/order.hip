@@ -26,9 +26,7 @@
 // leaf_hw ending the read at 768 B where it may, the compacted key list in the
 // dead page slot and ranks from broadcast 16 B LDS reads) and its validity
 // rule (value != kValueNull, front == rear entry version; src/Tree.cpp:461-540).
-// The page helpers are copies of export.hip's, which are copies of scan.hip's:
-// shared through a header they changed k_range's register allocation
-// (DESIGN.md "Ordered scans").
+// The page helpers and leaf_load are page_group.h's.
 //
 // Bounds.  Every chain walk is bounded by the allocated pages (max_pages),
 // every pointer by ptr_ok, a unit index by the unit count, and a page is read
@@ -37,77 +35,14 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
+#include "page_group.h"
 
 namespace shm {
 namespace dev {
 
 namespace {
 constexpr int kOWaves = 4;
-constexpr int kRG = 4;                        // queries per wave
-constexpr int kRL = kWave / kRG;              // lanes per query
-constexpr int kRE = 4;                        // leaf entries per lane
-constexpr int kRCD = kLeafEntry * kRE / 4;    // dwords of a lane's entry chunk
-constexpr int kRChunks = kPageSize / 16 / kRL;  // 16 B page chunks per lane
-static_assert(kRL * kRE >= kLeafCardinality, "entries per group");
-static_assert((kLeafCardinality + 1) * 8 <= (int)kPageSize, "key list");
 static_assert(kOrdFan == kRL, "one index word per lane of a query's group");
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-struct RPage {
-  u32x4 c[kRChunks];
-};
-
-// chunks 0..2 (bytes 0..767: the header and slots 0..39); chunk 3 (slots
-// 40..53 and the rear version) only when the leaf's occupancy bound says a
-// valid slot may lie there (layout.h leaf_hw: every slot >= hw is empty)
-constexpr uint32_t kChunk3Hw = 41;  // slot 40 ends past byte 767
-__device__ __forceinline__ void rload3(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  const uint8_t* b = arena + ga_offset(p) + 16 * li;
-#pragma unroll
-  for (int k = 0; k < kRChunks - 1; ++k)
-    w.c[k] = *reinterpret_cast<const u32x4*>(b + 16 * kRL * k);
-}
-__device__ __forceinline__ void rload_last(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  w.c[kRChunks - 1] =
-      *reinterpret_cast<const u32x4*>(arena + ga_offset(p) + 16 * li + 16 * kRL * (kRChunks - 1));
-}
-__device__ __forceinline__ void rstage(uint32_t* lp, int li, const RPage& w) {
-#pragma unroll
-  for (int k = 0; k < kRChunks; ++k) *reinterpret_cast<u32x4*>(lp + 4 * (li + kRL * k)) = w.c[k];
-}
-__device__ __forceinline__ uint64_t lds_u64(const uint32_t* lp, int d) {
-  return (uint64_t)lp[d] | ((uint64_t)lp[d + 1] << 32);
-}
-// header fields of a staged page (Tree.h:130-160; bytes 9..43)
-__device__ __forceinline__ uint64_t hdr_leftmost(const uint32_t* lp) {
-  const uint32_t a2 = lp[2], a3 = lp[3], b0 = lp[4];
-  return (uint64_t)((a2 >> 8) | (a3 << 24)) | ((uint64_t)((a3 >> 8) | (b0 << 24)) << 32);
-}
-__device__ __forceinline__ uint64_t hdr_sibling(const uint32_t* lp) {
-  const uint32_t b0 = lp[4], b1 = lp[5], b2 = lp[6];
-  return (uint64_t)((b0 >> 8) | (b1 << 24)) | ((uint64_t)((b1 >> 8) | (b2 << 24)) << 32);
-}
-// exclusive prefix of v over the 16 lanes of each query's group; *tot = group sum
-__device__ __forceinline__ uint32_t group_scan(uint32_t v, int li, uint32_t* tot) {
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < kRL; off <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)incl, off, kRL);
-    if (li >= off) incl += y;
-  }
-  *tot = (uint32_t)__shfl((int)incl, kRL - 1, kRL);
-  return incl - v;
-}
-// a leaf's bytes into w: its last 256 B only when its occupancy bound reaches
-// slot 40 (pages of a loaded image: kLeafHwFull, read whole)
-__device__ __forceinline__ void leaf_load(const OrderArgs& a, uint64_t p, int li, RPage& w,
-                                          uint32_t& hw) {
-  const uint32_t h = a.leaf_hw ? a.leaf_hw[ga_offset(p) >> 10] : kLeafHwFull;
-  rload3(a.arena, p, li, w);
-  if (h >= kChunk3Hw) rload_last(a.arena, p, li, w);
-  hw = h < (uint32_t)kLeafCardinality ? h : (uint32_t)kLeafCardinality;
-}
 
 // The index of the first word above x in level 0 of a pyramid, for the query
 // of group q (x is the same in its 16 lanes); *ok = false when a block held no

@@ -18,72 +18,20 @@
 // Along the leaf chain the sibling page is loaded into registers as soon as
 // the current header says the scan continues, so its HBM latency overlaps
 // the current leaf's compare and stores.  offsets == nullptr -> count only.
+//
+// The group's page helpers are page_group.h's.  The descent inside range_walk
+// has a copy in scan.hip (leaf_descend): called from here instead, it changes
+// k_range's register assignment, so it stays inline.
 #include "device_common.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
+#include "page_group.h"
 
 namespace shm {
 namespace dev {
 
 namespace {
 constexpr int kRangeWaves = 4;
-constexpr int kRG = 4;                        // scans per wave
-constexpr int kRL = kWave / kRG;              // lanes per scan
-constexpr int kRE = 4;                        // leaf entries per lane
-constexpr int kRCD = kLeafEntry * kRE / 4;    // dwords of a lane's entry chunk
-constexpr int kRChunks = kPageSize / 16 / kRL;  // 16 B page chunks per lane
-static_assert(kRL * kRE >= kLeafCardinality, "entries per group");
-
-struct RPage {
-  u32x4 c[kRChunks];
-};
-
-__device__ __forceinline__ void rload(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  const uint8_t* b = arena + ga_offset(p) + 16 * li;
-#pragma unroll
-  for (int k = 0; k < kRChunks; ++k) w.c[k] = *reinterpret_cast<const u32x4*>(b + 16 * kRL * k);
-}
-// chunks 0..2 (bytes 0..767: the header and slots 0..39); chunk 3 (slots
-// 40..53 and the rear version) only when the leaf's occupancy bound says a
-// valid slot may lie there (layout.h leaf_hw: every slot >= hw is empty)
-constexpr uint32_t kChunk3Hw = 41;  // slot 40 ends past byte 767
-__device__ __forceinline__ void rload3(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  const uint8_t* b = arena + ga_offset(p) + 16 * li;
-#pragma unroll
-  for (int k = 0; k < kRChunks - 1; ++k)
-    w.c[k] = *reinterpret_cast<const u32x4*>(b + 16 * kRL * k);
-}
-__device__ __forceinline__ void rload_last(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  w.c[kRChunks - 1] =
-      *reinterpret_cast<const u32x4*>(arena + ga_offset(p) + 16 * li + 16 * kRL * (kRChunks - 1));
-}
-__device__ __forceinline__ void rstage(uint32_t* lp, int li, const RPage& w) {
-#pragma unroll
-  for (int k = 0; k < kRChunks; ++k) *reinterpret_cast<u32x4*>(lp + 4 * (li + kRL * k)) = w.c[k];
-}
-__device__ __forceinline__ uint64_t lds_u64(const uint32_t* lp, int d) {
-  return (uint64_t)lp[d] | ((uint64_t)lp[d + 1] << 32);
-}
-// header fields of a staged page (Tree.h:130-160; bytes 9..43)
-__device__ __forceinline__ uint64_t hdr_leftmost(const uint32_t* lp) {
-  const uint32_t a2 = lp[2], a3 = lp[3], b0 = lp[4];
-  return (uint64_t)((a2 >> 8) | (a3 << 24)) | ((uint64_t)((a3 >> 8) | (b0 << 24)) << 32);
-}
-__device__ __forceinline__ uint64_t hdr_sibling(const uint32_t* lp) {
-  const uint32_t b0 = lp[4], b1 = lp[5], b2 = lp[6];
-  return (uint64_t)((b0 >> 8) | (b1 << 24)) | ((uint64_t)((b1 >> 8) | (b2 << 24)) << 32);
-}
-// exclusive prefix of v over the 16 lanes of each scan group; *tot = group sum
-__device__ __forceinline__ uint32_t group_scan(uint32_t v, int li, uint32_t* tot) {
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < kRL; off <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)incl, off, kRL);
-    if (li >= off) incl += y;
-  }
-  *tot = (uint32_t)__shfl((int)incl, kRL - 1, kRL);
-  return incl - v;
-}
 }  // namespace
 
 // Walks one scan per group of the wave (act: the group has one) from the
@@ -301,41 +249,6 @@ void launch_range(const RangeArgs& a, hipStream_t s) {
   const uint64_t per = (uint64_t)kRangeWaves * kRG;
   hipLaunchKernelGGL(k_range, dim3((unsigned)((a.n + per - 1) / per)), dim3(kRangeWaves * kWave),
                      0, s, a);
-}
-
-// zero-copy read-back (tree.cpp readback): one wave copies the words into
-// mapped host memory with vector stores, fences at system scope, then lane 0
-// publishes the sequence number the host spins on.  clear: each word is
-// taken by an atomic exchange with 0 (the error block: a bit another stream
-// sets after the exchange stays for the next read)
-__global__ void k_readback(uint32_t* dst, uint32_t* src, uint32_t nw, uint32_t* flag,
-                           uint32_t seq, int clear) {
-  for (uint32_t l = threadIdx.x; l < nw; l += blockDim.x)
-    dst[l] = clear ? atomicExch(src + l, 0u) : src[l];
-  const uint32_t l = threadIdx.x;
-  __threadfence_system();
-  // the fence's write-back performed before the flag (the returned exchanges
-  // above let the compiler drop the fence's own wait: MI355X_MICROARCH.md
-  // "Compiler hazard")
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (l == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-void launch_readback(uint32_t* dst, const uint32_t* src, uint32_t nw, uint32_t* flag,
-                     uint32_t seq, int clear, hipStream_t s) {
-  hipLaunchKernelGGL(k_readback, dim3(1), dim3(64), 0, s, dst, const_cast<uint32_t*>(src), nw,
-                     flag, seq, clear);
-}
-
-__global__ void k_add_u64(uint64_t* x, uint64_t n, uint64_t c) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] += c;
-}
-
-void launch_add_u64(uint64_t* x, uint64_t n, uint64_t c, hipStream_t s) {
-  if (n && c) hipLaunchKernelGGL(k_add_u64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                                 x, n, c);
 }
 
 }  // namespace dev

@@ -1,9 +1,10 @@
-// util.hip — batch bookkeeping kernels (segmentation with lock-ahead, tile
-// scans, multi-GPU routing, key generation).
+// route.hip — multi-GPU routing: what tree_route.cpp and shard*.cpp launch.
+// A key's owning shard, stable bucketing by owner, the fixed-capacity get
+// exchange, the routed insert's packing and the routed range scans' pieces,
+// sums and assembly.
 #include "device_common.h"
 #include "kernels.h"
-#include "upper_quick.h"
-#include "seg_tile.h"
+#include "seg_tile.h"  // segt::block_scan (k_range_sums)
 
 namespace shm {
 namespace dev {
@@ -13,193 +14,9 @@ constexpr int kT = 256;
 inline dim3 grid1(uint64_t n, int per = kT) {
   return dim3((unsigned)((n + per - 1) / per));
 }
+static_assert(kT == segt::kT, "segt::block_scan's block");
 }  // namespace
 
-// n_dev (nullable): the device-side op count, n its upper bound
-__device__ __forceinline__ uint64_t dev_n(const uint64_t* n_dev, uint64_t n) {
-  return n_dev ? *n_dev : n;
-}
-
-// ---- two-launch tile scans ---------------------------------------------------
-// A tile is kSegTile = 1024 elements, 4 consecutive per thread of a 256-thread
-// block.  Pass 1 stores each tile's sum; pass 2 adds the sums of the tiles
-// before it (<= n / 1024 words, read by the whole block) to a block scan.  No
-// look-back state to initialise, no temp storage, two launches in all.
-namespace {
-constexpr int kScanPer = (int)kSegTile / kT;
-static_assert(kScanPer * kT == (int)kSegTile, "tile shape");
-
-// exclusive scan of v over the block's 256 threads; *total = the block sum
-template <class T>
-__device__ __forceinline__ T block_scan(T v, T* total) {
-  __shared__ T ws[kT / kWave];
-  T incl = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const T y = __shfl_up(incl, off);
-    if (lane_id() >= off) incl += y;
-  }
-  const int w = threadIdx.x / kWave;
-  if (lane_id() == kWave - 1) ws[w] = incl;
-  __syncthreads();
-  T base = 0, sum = 0;
-#pragma unroll
-  for (int i = 0; i < kT / kWave; ++i) {
-    base += i < w ? ws[i] : T(0);
-    sum += ws[i];
-  }
-  __syncthreads();
-  *total = sum;
-  return base + incl - v;
-}
-
-}  // namespace
-
-
-// One launch: every 1024-op tile counts its staged heads, publishes the
-// count in its tagged word (chunk tag << 32 | count), sums the words of the
-// tiles before it (tile index = blockIdx, or a ticket when the tree passes a
-// counter, lookback_index; tree.cpp lb_ctr says which and why), and fills its
-// segments: seg_start / seg_page at each staged head, seg_end at its run's
-// last op (the count of staged heads up to and including that op is the
-// segment's position + 1).
-
-__global__ __launch_bounds__(kT) void k_seg_fill(const uint64_t* page, uint64_t n,
-                                                 const uint64_t* n_dev, uint64_t* lbw,
-                                                 uint32_t* seg_start, uint32_t* seg_end,
-                                                 uint64_t* seg_page, uint32_t* num_seg,
-                                                 const uint8_t* pnew, uint32_t tag,
-                                                 const uint32_t* any_new, uint32_t* err,
-                                                 UpperArgs q, int has_q, uint32_t* ids,
-                                                 uint32_t self_after, const uint64_t* ndel_src,
-                                                 uint64_t* ndel_dst) {
-  // the chunk's delete count into UpperCtl (k_upper's copy), before anything
-  // of this chunk publishes its op buffers free (below, or k_upper)
-  if (ndel_dst && blockIdx.x == 0 && threadIdx.x == 0) *ndel_dst = *ndel_src;
-  if (any_new && *any_new != tag) {  // no op of this chunk marked a page (every block)
-    if (blockIdx.x == 0) {
-      if (threadIdx.x == 0) *num_seg = 0;
-      if (has_q) seg_complete_unchanged(q);
-    }
-    return;
-  }
-  // the look-back's tile: a ticket, taken by every block past the check above
-  const uint32_t b = lookback_index(ids);
-  const uint64_t nv = dev_n(n_dev, n);
-  if ((uint64_t)b * kSegTile >= nv) {  // past the device count (the grid covers n)
-    if (nv == 0 && b == 0 && threadIdx.x == 0) *num_seg = 0;
-    return;
-  }
-  segt::seg_tile(page, nv, b, lbw, seg_start, seg_end, seg_page, num_seg, pnew, tag, self_after);
-}
-
-void launch_segment(const uint64_t* page, uint64_t n, const uint64_t* n_dev, uint64_t* lbw,
-                    uint32_t* seg_start, uint32_t* seg_end, uint64_t* seg_page,
-                    uint32_t* num_seg, const uint8_t* pnew, uint32_t tag,
-                    const uint32_t* any_new, uint32_t* err, hipStream_t s,
-                    const UpperArgs* quick, uint32_t* ids, uint32_t self_after,
-                    const uint64_t* ndel_src, uint64_t* ndel_dst) {
-  const UpperArgs q = quick ? *quick : UpperArgs{};
-  const int has_q = quick && any_new ? 1 : 0;
-  // at least one block: block 0 copies the delete count even for no ops
-  const uint64_t tiles = n ? seg_tiles(n) : 1;
-  hipLaunchKernelGGL(k_seg_fill, dim3((unsigned)tiles), dim3(kT), 0, s, page, n, n_dev, lbw,
-                     seg_start, seg_end, seg_page, num_seg, pnew, tag, any_new, err, q, has_q, ids,
-                     self_after, ndel_src, ndel_dst);
-}
-
-// Exclusive scan of u64 counts in one launch: every 1024-element tile
-// publishes its sum in a tagged word (tag << 48 | sum: a range scan's
-// counts total < 2^48), sums the words of the tiles before it (as
-// k_seg_fill) and writes its offsets; the thread holding n - 1 writes
-// tot = {total, *err} (nullable).
-__global__ __launch_bounds__(kT) void k_scan_u64(const uint64_t* in, uint64_t n, uint64_t* lbw,
-                                                 uint32_t tag, uint64_t* out,
-                                                 const uint32_t* err, uint64_t* tot,
-                                                 uint32_t* err_out, uint32_t* ids) {
-  __shared__ uint64_t s_pre[kT / kWave];
-  const uint32_t b = lookback_index(ids);  // the tile
-  const uint64_t i0 = (uint64_t)b * kSegTile + (uint64_t)threadIdx.x * kScanPer;
-  uint64_t v[kScanPer], c = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    v[j] = i0 + j < n ? in[i0 + j] : 0;
-    c += v[j];
-  }
-  uint64_t total;
-  const uint64_t local = block_scan<uint64_t>(c, &total);
-  constexpr uint64_t kMask = (1ull << 48) - 1;
-  const uint64_t tg = (uint64_t)(tag & 0xFFFFu) << 48;
-  if (threadIdx.x == 0)
-    __hip_atomic_store(lbw + b, tg | (total & kMask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  uint64_t pre = 0;
-  for (uint32_t x = threadIdx.x; x < b; x += kT) {
-    uint64_t w = 0;
-    for (uint32_t spin = 0;; ++spin) {
-      w = __hip_atomic_load(lbw + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((w & ~kMask) == tg) break;
-      if (spin > (1u << 24)) {
-        atomicOr(err_out, kErrScanSpin);
-        w = tg;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    pre += w & kMask;
-  }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) pre += __shfl_xor(pre, o);
-  if (lane_id() == 0) s_pre[threadIdx.x / kWave] = pre;
-  __syncthreads();
-  uint64_t pos = local;
-#pragma unroll
-  for (int w = 0; w < kT / kWave; ++w) pos += s_pre[w];
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    if (i0 + j < n) out[i0 + j] = pos;
-    pos += v[j];
-    if (tot && i0 + j + 1 == n) {
-      tot[0] = pos;
-      tot[1] = *err;
-    }
-  }
-}
-
-void launch_scan_u64_total(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* lbw,
-                           uint32_t tag, const uint32_t* err, uint64_t* tot, uint32_t* err_out,
-                           uint32_t* ids, hipStream_t s) {
-  if (!n) return;
-  hipLaunchKernelGGL(k_scan_u64, dim3((unsigned)seg_tiles(n)), dim3(kT), 0, s, in, n, lbw, tag, out,
-                     err, tot, err_out, ids);
-}
-
-// to_key without / with the modulus (test/benchmark.cpp:43-46)
-__global__ void k_gen_keys(uint64_t first, uint64_t n, uint64_t keyspace,
-                           uint64_t* out) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t h = cityhash64_u64(first + i) + 1;
-  out[i] = keyspace ? h % keyspace : h;
-}
-void launch_gen_keys(uint64_t first, uint64_t n, uint64_t keyspace,
-                     uint64_t* out, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_gen_keys, grid1(n), dim3(kT), 0, s, first, n, keyspace, out);
-}
-
-// keys[i] = to_key(ids[i]) for an arbitrary id array (zipf streams)
-__global__ void k_hash_ids(const uint64_t* ids, uint64_t n, uint64_t keyspace,
-                           uint64_t* out) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t h = cityhash64_u64(ids[i]) + 1;
-  out[i] = keyspace ? h % keyspace : h;
-}
-void launch_hash_ids(const uint64_t* ids, uint64_t n, uint64_t keyspace, uint64_t* out,
-                     hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_hash_ids, grid1(n), dim3(kT), 0, s, ids, n, keyspace, out);
-}
-
-// ---- multi-GPU routing -------------------------------------------------------
 // Equal slices (no splitters): shard s owns [s*2^64/P, (s+1)*2^64/P).
 __device__ __forceinline__ uint32_t owner_of(uint64_t k, uint32_t shards) {
   return (uint32_t)__umul64hi(k, (uint64_t)shards);
@@ -865,7 +682,7 @@ __global__ __launch_bounds__(kT) void k_range_sums(const uint64_t* rc, const uin
     uint64_t v = 0;
     for (uint64_t j = threadIdx.x; j < cap; j += kT) v += row[j];
     uint64_t tot;
-    (void)block_scan<uint64_t>(v, &tot);
+    (void)segt::block_scan<uint64_t>(v, &tot);
     if (threadIdx.x == 0) rw[b] = tot;
     return;
   }
@@ -952,72 +769,6 @@ void launch_range_pitch(const uint64_t* rvals, const uint64_t* rw, uint32_t P, u
   if (bx == 0) bx = 1;
   hipLaunchKernelGGL(k_range_pitch, dim3((unsigned)bx, P), dim3(kT), 0, s, rvals, rw, P, pitch,
                      out, rvcap, vals_cap, status);
-}
-
-// ---- Tree::lock_bench (src/Tree.cpp:310-321): take and release the lock word
-// of each key, lock[CityHash64(key) % num_locks], as try_lock_addr /
-// unlock_addr do (Tree.cpp:205-264) on the HBM lock table: a word is free
-// when it holds <= tag (the epoch tags of the insert chunks, insert.hip),
-// taken as tag | 1 by atomicCAS, released by storing tag.  Lanes of one wave
-// that share a word take it in turn (a lane releases in the iteration it
-// acquired, so the wave never waits on itself).  Spins are bounded.
-__global__ __launch_bounds__(kT) void k_lock_bench(const uint64_t* keys, uint64_t n,
-                                                   uint64_t* locks, uint32_t num_locks,
-                                                   uint64_t tag, uint32_t* err) {
-  const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
-  bool done = i >= n;
-  unsigned long long* w = nullptr;
-  if (!done)
-    w = reinterpret_cast<unsigned long long*>(locks) + cityhash64_u64(keys[i]) % num_locks;
-  const unsigned long long mine = (unsigned long long)(tag | 1ull);
-  for (uint32_t spin = 0; spin < kMaxLockSpins; ++spin) {
-    if (!done) {
-      const unsigned long long cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur <= (unsigned long long)tag && atomicCAS(w, cur, mine) == cur) {
-        __hip_atomic_store(w, (unsigned long long)tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        done = true;
-      }
-    }
-    if (!ballot(!done)) return;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  if (!done) atomicOr(err, kErrLock);
-}
-void launch_lock_bench(const uint64_t* keys, uint64_t n, uint64_t* locks, uint32_t num_locks,
-                       uint64_t tag, uint32_t* err, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_lock_bench, grid1(n), dim3(kT), 0, s, keys, n, locks, num_locks, tag, err);
-}
-
-// ---- diagnostics: a window marker for profiles (shm__mark) -------------------
-// One empty wave whose dispatch names a window's edge in a kernel trace or a
-// counter collection (tools/fold_roofline.py keeps the dispatches between
-// tag 1 and tag 2).
-__global__ void k_mark(uint32_t tag) { (void)tag; }
-void launch_mark(uint32_t tag, hipStream_t s) {
-  hipLaunchKernelGGL(k_mark, dim3(1), dim3(kWave), 0, s, tag);
-}
-
-// ---- diagnostics: a kernel that holds CUs (shm__hog) -----------------------------
-// Each block declares a whole CU's LDS (160 KiB), so no other block that uses
-// LDS fits its CU while it runs, and spins on the 100 MHz wall clock until
-// `ticks` have passed since it started (bounded: every wave leaves).  n
-// blocks therefore take n CUs away from the kernels of other streams for that
-// long (tests/test_gpu_parity.py::test_split_insert_beside_cu_hog).
-constexpr uint32_t kHogLdsWords = 160 * 1024 / 4;
-__global__ __launch_bounds__(kWave) void k_hog(uint64_t ticks, uint32_t* sink) {
-  __shared__ uint32_t s_pad[kHogLdsWords];
-  s_pad[threadIdx.x] = threadIdx.x;
-  const uint64_t t0 = wall_clock64();
-  uint32_t spins = 0;
-  while (wall_clock64() - t0 < ticks) {
-    __builtin_amdgcn_s_sleep(8);
-    ++spins;
-  }
-  // keep the LDS array alive; never true for a real run (spins > 0)
-  if (spins == 0xFFFFFFFFu) sink[0] = s_pad[(threadIdx.x * 7) % kHogLdsWords];
-}
-void launch_hog(uint32_t n, uint64_t ticks, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_hog, dim3(n), dim3(kWave), 0, s, ticks, nullptr);
 }
 
 }  // namespace dev

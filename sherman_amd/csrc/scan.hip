@@ -11,9 +11,9 @@
 // moved through registers into the group's 1 KB LDS slot, the start leaf from
 // the leaf directory (or a descent from the covering internal page / the
 // root), B-link right turns on a stale start, leaf_hw bounding the page read.
-// The page helpers and the descent are copies of range.hip's: shared through
-// a header they changed k_range's register allocation (DESIGN.md "Ordered
-// scans"), and k_range is the benchmark's C5 kernel.
+// The page helpers are page_group.h's.  leaf_descend is a copy of the descent
+// inside range.hip's range_walk: called from there, it changes the register
+// assignment of k_range, the benchmark's C5 kernel.
 //
 // Order.  Leaves are ordered against each other by their fences; inside a
 // leaf the valid slots are not (updates land in place, inserts take the first
@@ -38,73 +38,13 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
+#include "page_group.h"
 
 namespace shm {
 namespace dev {
 
 namespace {
 constexpr int kScanWaves = 4;
-constexpr int kRG = 4;                        // scans per wave
-constexpr int kRL = kWave / kRG;              // lanes per scan
-constexpr int kRE = 4;                        // leaf entries per lane
-constexpr int kRCD = kLeafEntry * kRE / 4;    // dwords of a lane's entry chunk
-constexpr int kRChunks = kPageSize / 16 / kRL;  // 16 B page chunks per lane
-static_assert(kRL * kRE >= kLeafCardinality, "entries per group");
-// the hit keys of one leaf, padded to a pair, fit the page slot
-static_assert((kLeafCardinality + 1) * 8 <= (int)kPageSize, "key list");
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-struct RPage {
-  u32x4 c[kRChunks];
-};
-
-__device__ __forceinline__ void rload(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  const uint8_t* b = arena + ga_offset(p) + 16 * li;
-#pragma unroll
-  for (int k = 0; k < kRChunks; ++k) w.c[k] = *reinterpret_cast<const u32x4*>(b + 16 * kRL * k);
-}
-// chunks 0..2 (bytes 0..767: the header and slots 0..39); chunk 3 (slots
-// 40..53 and the rear version) only when the leaf's occupancy bound says a
-// valid slot may lie there (layout.h leaf_hw: every slot >= hw is empty)
-constexpr uint32_t kChunk3Hw = 41;  // slot 40 ends past byte 767
-__device__ __forceinline__ void rload3(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  const uint8_t* b = arena + ga_offset(p) + 16 * li;
-#pragma unroll
-  for (int k = 0; k < kRChunks - 1; ++k)
-    w.c[k] = *reinterpret_cast<const u32x4*>(b + 16 * kRL * k);
-}
-__device__ __forceinline__ void rload_last(const uint8_t* arena, uint64_t p, int li, RPage& w) {
-  w.c[kRChunks - 1] =
-      *reinterpret_cast<const u32x4*>(arena + ga_offset(p) + 16 * li + 16 * kRL * (kRChunks - 1));
-}
-__device__ __forceinline__ void rstage(uint32_t* lp, int li, const RPage& w) {
-#pragma unroll
-  for (int k = 0; k < kRChunks; ++k) *reinterpret_cast<u32x4*>(lp + 4 * (li + kRL * k)) = w.c[k];
-}
-__device__ __forceinline__ uint64_t lds_u64(const uint32_t* lp, int d) {
-  return (uint64_t)lp[d] | ((uint64_t)lp[d + 1] << 32);
-}
-// header fields of a staged page (Tree.h:130-160; bytes 9..43)
-__device__ __forceinline__ uint64_t hdr_leftmost(const uint32_t* lp) {
-  const uint32_t a2 = lp[2], a3 = lp[3], b0 = lp[4];
-  return (uint64_t)((a2 >> 8) | (a3 << 24)) | ((uint64_t)((a3 >> 8) | (b0 << 24)) << 32);
-}
-__device__ __forceinline__ uint64_t hdr_sibling(const uint32_t* lp) {
-  const uint32_t b0 = lp[4], b1 = lp[5], b2 = lp[6];
-  return (uint64_t)((b0 >> 8) | (b1 << 24)) | ((uint64_t)((b1 >> 8) | (b2 << 24)) << 32);
-}
-// exclusive prefix of v over the 16 lanes of each scan group; *tot = group sum
-__device__ __forceinline__ uint32_t group_scan(uint32_t v, int li, uint32_t* tot) {
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < kRL; off <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)incl, off, kRL);
-    if (li >= off) incl += y;
-  }
-  *tot = (uint32_t)__shfl((int)incl, kRL - 1, kRL);
-  return incl - v;
-}
 
 // Descends each group's scan (act: the group has one) from the leaf
 // directory / the root to the leaf whose fences hold lo; on return w holds

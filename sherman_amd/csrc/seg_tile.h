@@ -1,6 +1,7 @@
 // seg_tile.h — one 1024-op tile of the insert segmentation (the staged
 // segments: runs of ops on one page that gets a new key): k_seg_fill's body
-// (util.hip, one tile per block).
+// (tile_scan.hip, one tile per block).  Its block_scan also serves k_scan_u64
+// there and route.hip's k_range_sums.
 // (Round 5 measured a one-wave tile, 16 ops per lane at 32 VGPRs: 23.6
 // against 13.5 us alone in C5's profile window, and no better beside the
 // ordering, 32-33 us either way; the 256-thread tile stays.  Holding the

@@ -3,7 +3,7 @@
 // counters zeroed, the superblock's batch count, the host mirror's tags.
 // Shared by k_upper and by the segmentation kernel, whose block 0 completes
 // a chunk without a new key or a delete (C3's chunks) so that the upsert
-// kernel and k_upper return at once (util.hip k_seg_fill).
+// kernel and k_upper return at once (tile_scan.hip k_seg_fill).
 #pragma once
 #include "device_common.h"
 #include "kernels.h"

@@ -1,5 +1,5 @@
 """Host model of splitter routing and of the rebalance plan (numpy / Python
-ints only): what util.hip's owner search, shm_route_bucket_bounds and
+ints only): what route.hip's owner search, shm_route_bucket_bounds and
 shm_rebalance_plan must compute.
 
 Owner rule: shard p owns [b[p], b[p + 1]) with b[0] = 0, b[P] = 2^64 and
