@@ -19,6 +19,7 @@
 // the leaves, 1088 B written per leaf: bound by HBM traffic, a third to a half
 // of it reads (DESIGN.md §3.3.1 has the measured rates).
 #include "device_common.h"
+#include "page_io.h"
 #include "kernels.h"
 
 namespace shm {

@@ -34,7 +34,7 @@
 //     page (any slot order) and its entries stay as they are, and the bucket
 //     table takes each op key's pair from the tree instead of from the op.
 // Every entry a get trusts still only names slots to read: a get that does
-// not find its key there walks the summary path (get.hip), so the upkeep is
+// not find its key there walks the summary path (get_sum.hip), so the upkeep is
 // about cost, never about results.  Prefixes of a split page without keys
 // are left as they were: their stale entries can only send a miss on a
 // B-link right move.

@@ -39,6 +39,7 @@
 // every pointer by ptr_ok, and a page is read as a level-L page only when its
 // header says so: a corrupt image ends with an error bit.
 #include "device_common.h"
+#include "page_io.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
 #include "page_group.h"
@@ -164,12 +165,12 @@ __global__ __launch_bounds__(kXWaves* kWave) void k_export_leaf(ExportArgs a) {
     }
     if (act) {
       // read as a leaf only when its header says so
-      if (hdr_leftmost(lp) != 0 || ((lp[6] >> 8) & 0xFFu) != 0) {
+      if (hdr_leftmost(lp) != 0 || hdr_level(lp) != 0) {
         err |= kErrInconsistent;
         act = false;
       } else {
         sibling = hdr_sibling(lp);
-        const uint64_t highest = lds_u64(lp, 9);
+        const uint64_t highest = hdr_highest(lp);
         more = sibling != 0 && highest < bound && highest <= hi;
         if (more && (++hops >= a.max_pages || !ptr_ok(sibling, a.node, a.arena_bytes))) {
           err |= kErrBadPtr;

@@ -37,6 +37,8 @@
 // level's batch.  Nothing here waits for the host; the superblock and a
 // mapped host mirror are updated at the end of the launch.
 #include "device_common.h"
+#include "page_io.h"
+#include "sum_line.h"
 #include "kernels.h"
 #include "split_wave.h"
 #include "upper_quick.h"

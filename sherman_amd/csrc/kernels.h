@@ -1,8 +1,8 @@
 // kernels.h — launch interface between the host runtime (tree*.cpp,
-// shard*.cpp) and the HIP kernels (get.hip, locate.hip, isort.hip,
-// partition.hip, upsert.hip, insert.hip, leafdir.hip, tile_scan.hip,
-// route.hip, range.hip, scan.hip, bulk.hip, export.hip, order.hip,
-// service.hip).  Each section below names the unit that defines what it
+// shard*.cpp) and the HIP kernels (get.hip, get_sum.hip, get_side.hip,
+// locate.hip, isort.hip, partition.hip, upsert.hip, insert.hip, leafdir.hip,
+// tile_scan.hip, route.hip, range.hip, scan.hip, bulk.hip, export.hip,
+// order.hip, service.hip).  Each section below names the unit that defines what it
 // declares.  Host-only types; no torch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,7 +13,8 @@
 namespace shm {
 namespace dev {
 
-// ---- gets, locate, leaf directory (get.hip, locate.hip, leafdir.hip) ----------
+// ---- gets, locate, leaf directory (get.hip, get_sum.hip, get_side.hip,
+// locate.hip, leafdir.hip) ---------------------------------------------------
 // the key-value bucket table's format (valtab.h): 8 slots of (key, value) per
 // 128 B bucket; the build's counter words
 constexpr int kVtSlots = 8;
@@ -115,7 +116,8 @@ enum IdxStat {
   kIdxDirFp,           // found through the directory entry's fingerprints
   kIdxStats
 };
-// top-of-tree table for the LDS replica: every page of the deepest level
+// top-of-tree table for k_get_sum's LDS replica (get_side.hip: what the gets
+// read beside the pages, rebuilt from the pages): every page of the deepest level
 // whose page count fits max_n, in key order: keys[i] = its lowest fence,
 // pages[i] = its page index; *n_out = the count, *level_out its level
 void launch_top(const uint8_t* arena, uint64_t arena_bytes, uint16_t node, uint64_t root,
@@ -129,12 +131,12 @@ void launch_get(const WalkArgs& a, uint64_t n, hipStream_t s);
 // words: one per block + one per wave, WalkArgs.clk)
 constexpr int kGetSumTPB = 256;
 uint64_t get_sum_blocks(uint64_t n);
-// batched get over the leaf summaries, lane = query (get.hip): directory
+// batched get over the leaf summaries, lane = query (get_sum.hip): directory
 // entry, summary line, matching entries; results in input order
 void launch_get_sum(const WalkArgs& a, uint64_t n, hipStream_t s, hipEvent_t ev0 = nullptr,
                     hipEvent_t ev1 = nullptr);
 // rebuild the summaries of pages [1, pages) from the page bytes (a loaded
-// image), one wave per page; leaf[p] != 0 (device bytes, one per page) names
+// image; get_side.hip), one wave per page; leaf[p] != 0 (device bytes, one per page) names
 // the leaves the image reaches from its root: only those get a line
 void launch_sum_rebuild(const uint8_t* arena, uint64_t pages, const uint8_t* leaf, uint8_t* sum,
                         hipStream_t s);

@@ -87,7 +87,7 @@ constexpr uint32_t kSumOffFp = 9;
 constexpr uint8_t kSumLeaf = 0xA5;
 static_assert(kSumOffFp + kLeafCardinality <= kSumBytes, "summary line");
 // leaf directory entries (leafdir.hip): 64 B = kDirWords u64 each; count
-// word flag: the entry is in fingerprint form (device_common.h dir_fp_cand)
+// word flag: the entry is in fingerprint form (dir_entry.h dir_fp_cand)
 constexpr uint64_t kDirWords = 8;
 constexpr uint32_t kDirFp = 0x100u;
 // pair form (a read phase's build, leafdir.hip k_dir_pairs): the leaf list
@@ -108,7 +108,7 @@ constexpr uint32_t kDirFix = 0x800u;
 // which a leaf count <= 2 leaves unread), key1 and value1 in bytes 48..63
 // (pairs 8..15, unused at <= 2 pairs).  The pairs stay at bytes 32..35.  An
 // exact directory's get of such a prefix is answered by the entry alone
-// (get.hip).  While the entry is usable and its pair count is <= kDirValMax
+// (get_sum.hip).  While the entry is usable and its pair count is <= kDirValMax
 // the copies equal the tree (dir_upkeep.h); a third key ends the form
 // through the count, the flag itself stays (it then only says that bytes
 // 48..63 are not pair slots: the entry holds 8 pairs until a repair or a

@@ -10,7 +10,7 @@
 // pg_i = page index of leaf i (GlobalAddress offset / 1 KB), t_i = the top
 // 32 bits of (sep_i - lo_p) with sep_i = lowest fence of leaf i (all of it
 // when shift <= 32).  A query k starts at leaf i for the largest i < n whose
-// t_i is below k's (dir_start, device_common.h).  n == 0 marks a prefix
+// t_i is below k's (dir_start, dir_entry.h).  n == 0 marks a prefix
 // spanning more than four leaves: pg0 is then the deepest internal page whose
 // fences cover the whole prefix.
 //
@@ -21,6 +21,8 @@
 // rebuilds the directory when the tree has grown enough to make the extra
 // hops matter.
 #include "device_common.h"
+#include "page_fields.h"
+#include "page_io.h"
 #include "dir_upkeep.h"
 #include "kernels.h"
 #include "valtab.h"
@@ -29,20 +31,12 @@ namespace shm {
 namespace dev {
 
 namespace {
-__device__ __forceinline__ uint64_t pg64(const uint8_t* pg, int o) {  // 4-aligned
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(pg + o);
-  return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-}
-__device__ __forceinline__ uint64_t pg64_b1(const uint8_t* pg, int d) {  // byte 4d+1
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(pg) + d;
-  return (uint64_t)((w[0] >> 8) | (w[1] << 24)) | ((uint64_t)((w[1] >> 8) | (w[2] << 24)) << 32);
-}
 // internal_page_search (Tree.cpp:665-685): number of keys <= x
 __device__ __forceinline__ int keys_le(const uint8_t* pg, int cnt, uint64_t x) {
   int lo = 0, hi = cnt;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if (pg64(pg, kOffRecords + kInternalEntry * mid) <= x)
+    if (rec_key(page_dw(pg), mid) <= x)
       lo = mid + 1;
     else
       hi = mid;
@@ -81,10 +75,10 @@ __global__ __launch_bounds__(256) void k_leaf_dir(const uint8_t* __restrict__ ar
   for (int it = 0; it < 4096; ++it) {
     if (!ptr_ok(ptr, node, arena_bytes)) break;
     const uint8_t* pg = arena + ga_offset(ptr);
-    const uint64_t leftmost = pg64_b1(pg, 2);
-    const uint64_t sibling = pg64_b1(pg, 4);
-    const uint64_t highest = pg64(pg, kOffHighest);
-    if (hinted && (leftmost == 0 || pg[kOffLevel] != 1 || lo < pg64(pg, kOffLowest))) {
+    const uint64_t leftmost = hdr_leftmost(page_dw(pg));
+    const uint64_t sibling = hdr_sibling(page_dw(pg));
+    const uint64_t highest = hdr_highest(page_dw(pg));
+    if (hinted && (leftmost == 0 || pg[kOffLevel] != 1 || lo < hdr_lowest(page_dw(pg)))) {
       // not a level-1 page on lo's path any more (the root page grew a
       // level): descend from the root
       hinted = false;
@@ -106,7 +100,7 @@ __global__ __launch_bounds__(256) void k_leaf_dir(const uint8_t* __restrict__ ar
       // the deepest internal page whose fences hold the whole prefix (lo is
       // past its lowest on the path): the start of a prefix of > 4 leaves
       if (hi < highest) cover = ptr;
-      ptr = c == 0 ? leftmost : pg64(pg, kOffRecords + kInternalEntry * (c - 1) + 8);
+      ptr = c == 0 ? leftmost : rec_ptr(page_dw(pg), c - 1);
       hinted = false;  // below the hinted level now
       continue;
     }
@@ -121,9 +115,9 @@ __global__ __launch_bounds__(256) void k_leaf_dir(const uint8_t* __restrict__ ar
       }
       const uint8_t* sp = arena + ga_offset(sib);
       out[n] = sib;
-      out[3 + n] = pg64(sp, kOffLowest);  // sep_n = lowest of ptr_n
-      h = pg64(sp, kOffHighest);
-      sib = pg64_b1(sp, 4);
+      out[3 + n] = hdr_lowest(page_dw(sp));  // sep_n = lowest of ptr_n
+      h = hdr_highest(page_dw(sp));
+      sib = hdr_sibling(page_dw(sp));
       ++n;
     }
     if (n <= 4) {
@@ -231,7 +225,7 @@ __device__ __forceinline__ bool swept_leaf(const uint8_t* __restrict__ arena,
   // (both loads issued before either is tested: no dependent round more)
   const uint8_t tag = sum[pi * kSumBytes + kSumOffTag];
   const uint8_t* pg = arena + (pi << 10);
-  const bool leaf = pg[kOffLevel] == 0 && pg64_b1(pg, 2) == 0;  // level 0, no leftmost
+  const bool leaf = pg[kOffLevel] == 0 && hdr_leftmost(page_dw(pg)) == 0;  // level 0, no leftmost
   return tag == kSumLeaf && leaf;
 }
 

@@ -33,6 +33,10 @@
 #include <stdlib.h>
 
 #include "device_common.h"
+#include "dir_entry.h"
+#include "page_fields.h"
+#include "page_io.h"
+#include "sum_line.h"
 #include "kernels.h"
 
 namespace shm {
@@ -41,10 +45,6 @@ namespace dev {
 namespace {
 
 constexpr int kLocBlock = 256;
-
-__device__ __forceinline__ uint64_t g_u64(const uint32_t* p, int d) {
-  return (uint64_t)p[d] | ((uint64_t)p[d + 1] << 32);
-}
 
 }  // namespace
 
@@ -175,14 +175,15 @@ __device__ __forceinline__ void locate_body(const WalkArgs& a) {
         break;
       }
     }
+    // page_fields.h's hdr_fields over dwords 2..10 (A.z .. C.z), restated:
+    // through the struct reader (or u64_of for the fences) the kernel's
+    // register allocation changes, and a kernel the bench times stays as it is
     const u32x4 A = *reinterpret_cast<const u32x4*>(pg);      // dwords 0..3
     const u32x4 B = *reinterpret_cast<const u32x4*>(pg + 4);  // dwords 4..7
     const u32x4 C = *reinterpret_cast<const u32x4*>(pg + 8);  // dwords 8..11
-    const uint2 Z = *reinterpret_cast<const uint2*>(pg + 254);
-    const uint64_t leftmost = (uint64_t)((A.z >> 8) | (A.w << 24)) |
-                              ((uint64_t)((A.w >> 8) | (B.x << 24)) << 32);
-    const uint64_t sibling = (uint64_t)((B.x >> 8) | (B.y << 24)) |
-                             ((uint64_t)((B.y >> 8) | (B.z << 24)) << 32);
+    const uint2 Z = *reinterpret_cast<const uint2*>(pg + kDwLeafRear);  // both rear versions
+    const uint64_t leftmost = u64_b1(A.z, A.w, B.x);
+    const uint64_t sibling = u64_b1(B.x, B.y, B.z);
     const int level = (int)((B.z >> 8) & 0xFF);  // byte 25
     const int cnt = (int)(int16_t)(B.z >> 16) + 1;
     const uint64_t lowest = (uint64_t)B.w | ((uint64_t)C.x << 32);
@@ -219,10 +220,10 @@ __device__ __forceinline__ void locate_body(const WalkArgs& a) {
     for (int step = 32; step > 0; step >>= 1) {
       const int idx = pos + step - 1;
       const int ci = idx < 60 ? idx : 60;
-      const uint64_t kk = g_u64(pg, 11 + 4 * ci);
+      const uint64_t kk = u64_at(pg, rec_key_dw(ci));
       pos += (idx < cnt && kk <= k) ? step : 0;
     }
-    ptr = pos == 0 ? leftmost : g_u64(pg, 13 + 4 * (pos - 1));
+    ptr = pos == 0 ? leftmost : u64_at(pg, rec_ptr_dw(pos - 1));
   }
   if (err) atomicOr(a.err, err);
   a.out_page[i] = out;

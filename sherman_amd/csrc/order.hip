@@ -93,12 +93,12 @@ __device__ __forceinline__ void walk_below(const OrderArgs& a, bool act, uint64_
     uint32_t c = 0;  // below xa in the low half, below xb in the high half
     if (act) {
       // read as a leaf only when its header says so
-      if (hdr_leftmost(lp) != 0 || ((lp[6] >> 8) & 0xFFu) != 0) {
+      if (hdr_leftmost(lp) != 0 || hdr_level(lp) != 0) {
         err |= kErrInconsistent;
         act = false;
       } else {
         sibling = hdr_sibling(lp);
-        const uint64_t highest = lds_u64(lp, 9);
+        const uint64_t highest = hdr_highest(lp);
         more = sibling != 0 && highest < bound && highest < xb;
         if (more && (++hops >= a.max_pages || !ptr_ok(sibling, a.node, a.arena_bytes))) {
           err |= kErrBadPtr;
@@ -276,12 +276,12 @@ __global__ __launch_bounds__(kOWaves* kWave) void k_select(OrderArgs a) {
     }
     if (act) {
       // read as a leaf only when its header says so
-      if (hdr_leftmost(lp) != 0 || ((lp[6] >> 8) & 0xFFu) != 0) {
+      if (hdr_leftmost(lp) != 0 || hdr_level(lp) != 0) {
         err |= kErrInconsistent;
         act = false;
       } else {
         sibling = hdr_sibling(lp);
-        const uint64_t highest = lds_u64(lp, 9);
+        const uint64_t highest = hdr_highest(lp);
         more = sibling != 0 && highest < bound;
         if (more && (++hops >= a.max_pages || !ptr_ok(sibling, a.node, a.arena_bytes))) {
           err |= kErrBadPtr;

@@ -8,8 +8,8 @@
 // chunks of the group's page: chunks li, li + 16, li + 32 and li + 48 (RPage;
 // 256 B coalesced per group per load).  The page goes through those registers
 // into the group's 1 KB LDS slot (rstage), where the header fields are read
-// (hdr_*, lds_u64) and each lane takes its four consecutive 18 B entries
-// (leaf_chunk.h).  Chunk 3, the page's last 256 B, is read only when the
+// (page_fields.h: hdr_*, rec_key, rec_ptr) and each lane takes its four
+// consecutive 18 B entries (leaf_chunk.h).  Chunk 3, the page's last 256 B, is read only when the
 // leaf's occupancy bound says a valid slot may lie there (rload3 +
 // rload_last, leaf_load); rload reads the whole page.
 //
@@ -18,6 +18,7 @@
 #pragma once
 #include "device_common.h"
 #include "kernels.h"
+#include "page_fields.h"
 
 namespace shm {
 namespace dev {
@@ -60,18 +61,6 @@ __device__ __forceinline__ void rload_last(const uint8_t* arena, uint64_t p, int
 __device__ __forceinline__ void rstage(uint32_t* lp, int li, const RPage& w) {
 #pragma unroll
   for (int k = 0; k < kRChunks; ++k) *reinterpret_cast<u32x4*>(lp + 4 * (li + kRL * k)) = w.c[k];
-}
-__device__ __forceinline__ uint64_t lds_u64(const uint32_t* lp, int d) {
-  return (uint64_t)lp[d] | ((uint64_t)lp[d + 1] << 32);
-}
-// header fields of a staged page (Tree.h:130-160; bytes 9..43)
-__device__ __forceinline__ uint64_t hdr_leftmost(const uint32_t* lp) {
-  const uint32_t a2 = lp[2], a3 = lp[3], b0 = lp[4];
-  return (uint64_t)((a2 >> 8) | (a3 << 24)) | ((uint64_t)((a3 >> 8) | (b0 << 24)) << 32);
-}
-__device__ __forceinline__ uint64_t hdr_sibling(const uint32_t* lp) {
-  const uint32_t b0 = lp[4], b1 = lp[5], b2 = lp[6];
-  return (uint64_t)((b0 >> 8) | (b1 << 24)) | ((uint64_t)((b1 >> 8) | (b2 << 24)) << 32);
 }
 // exclusive prefix of v over the 16 lanes of each group; *tot = group sum
 __device__ __forceinline__ uint32_t group_scan(uint32_t v, int li, uint32_t* tot) {

@@ -23,6 +23,7 @@
 // has a copy in scan.hip (leaf_descend): called from here instead, it changes
 // k_range's register assignment, so it stays inline.
 #include "device_common.h"
+#include "dir_entry.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
 #include "page_group.h"
@@ -72,23 +73,23 @@ __device__ __forceinline__ uint64_t range_walk(const RangeArgs& a, bool act, uin
     wave_lds_sync();
     if (desc) {
       const uint64_t sibling = hdr_sibling(lp);
-      const uint64_t highest = lds_u64(lp, 9);
+      const uint64_t highest = hdr_highest(lp);
       const uint64_t leftmost = hdr_leftmost(lp);
       uint64_t np = 0;
       if (lo >= highest && sibling) {
         np = sibling;
       } else if (leftmost != 0) {
         // internal page (Tree.cpp:665-685): child = number of keys <= lo
-        const int last = (int)(int16_t)(lp[6] >> 16);
+        const int last = hdr_last_index(lp);
         uint32_t c = 0;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const int j = li + kRL * m;
-          c += (j <= last && j < kInternalCardinality && lds_u64(lp, 11 + 4 * j) <= lo) ? 1u : 0u;
+          c += (j <= last && j < kInternalCardinality && rec_key(lp, j) <= lo) ? 1u : 0u;
         }
         uint32_t tot;
         (void)group_scan(c, li, &tot);
-        np = tot == 0 ? leftmost : lds_u64(lp, 13 + 4 * ((int)tot - 1));
+        np = tot == 0 ? leftmost : rec_ptr(lp, (int)tot - 1);
       }
       if (np) {
         if (++hops > kMaxRounds || !ptr_ok(np, a.node, a.arena_bytes)) {
@@ -130,7 +131,7 @@ __device__ __forceinline__ uint64_t range_walk(const RangeArgs& a, bool act, uin
     }
     if (act) {
       sibling = hdr_sibling(lp);
-      const uint64_t highest = lds_u64(lp, 9);
+      const uint64_t highest = hdr_highest(lp);
       more = sibling != 0 && highest <= hi;
       if (more) {
         if (++hops > (1 << 24) || !ptr_ok(sibling, a.node, a.arena_bytes)) {

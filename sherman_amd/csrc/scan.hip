@@ -36,6 +36,7 @@
 // k_rscan (shm_rscan_batch), below k_scan, reads the same order downwards with
 // the same helpers: its comment gives the step to the left.
 #include "device_common.h"
+#include "dir_entry.h"
 #include "kernels.h"
 #include "leaf_chunk.h"
 #include "page_group.h"
@@ -76,23 +77,23 @@ __device__ __forceinline__ void leaf_descend(const ScanArgs& a, bool& act, uint6
     wave_lds_sync();
     if (desc) {
       const uint64_t sibling = hdr_sibling(lp);
-      const uint64_t highest = lds_u64(lp, 9);
+      const uint64_t highest = hdr_highest(lp);
       const uint64_t leftmost = hdr_leftmost(lp);
       uint64_t np = 0;
       if (lo >= highest && sibling) {
         np = sibling;
       } else if (leftmost != 0) {
         // internal page (Tree.cpp:665-685): child = number of keys <= lo
-        const int last = (int)(int16_t)(lp[6] >> 16);
+        const int last = hdr_last_index(lp);
         uint32_t c = 0;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const int j = li + kRL * m;
-          c += (j <= last && j < kInternalCardinality && lds_u64(lp, 11 + 4 * j) <= lo) ? 1u : 0u;
+          c += (j <= last && j < kInternalCardinality && rec_key(lp, j) <= lo) ? 1u : 0u;
         }
         uint32_t tot;
         (void)group_scan(c, li, &tot);
-        np = tot == 0 ? leftmost : lds_u64(lp, 13 + 4 * ((int)tot - 1));
+        np = tot == 0 ? leftmost : rec_ptr(lp, (int)tot - 1);
       }
       if (np) {
         if (++hops > kMaxRounds || !ptr_ok(np, a.node, a.arena_bytes)) {
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(kScanWaves* kWave) void k_scan(ScanArgs a) {
     }
     if (act) {
       sibling = hdr_sibling(lp);
-      const uint64_t highest = lds_u64(lp, 9);
+      const uint64_t highest = hdr_highest(lp);
       more = sibling != 0 && highest <= hi;
       if (more && (++hops > (1 << 24) || !ptr_ok(sibling, a.node, a.arena_bytes))) {
         err |= kErrBadPtr;
@@ -289,7 +290,7 @@ k_rscan(ScanArgs a) {
       ev[j] = 0;
     }
     if (act) {
-      const uint64_t lowest = lds_u64(lp, 7);  // before the slot becomes the key list
+      const uint64_t lowest = hdr_lowest(lp);  // before the slot becomes the key list
       uint32_t D[kRCD];
       const uint32_t* ep = lp + (kOffRecords + kLeafEntry * ebase) / 4;
 #pragma unroll

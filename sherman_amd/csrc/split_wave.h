@@ -4,6 +4,9 @@
 // reference citations.
 #pragma once
 #include "device_common.h"
+#include "dir_entry.h"
+#include "page_io.h"
+#include "sum_line.h"
 #include "kernels.h"
 
 namespace shm {

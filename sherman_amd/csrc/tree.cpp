@@ -1,8 +1,8 @@
 // tree.cpp — host runtime behind the C-ABI (include/sherman_amd.h).
 //
 // Owns one shard's HBM page arena, lock table and batch workspace, and issues
-// the kernels of get.hip / isort.hip / upsert.hip / insert.hip / range.hip /
-// tile_scan.hip / service.hip.  The roles of the reference's DSM (include/DSM.h:33-176: remote
+// the kernels of get.hip / get_sum.hip / get_side.hip / isort.hip /
+// upsert.hip / insert.hip / range.hip / tile_scan.hip / service.hip.  The roles of the reference's DSM (include/DSM.h:33-176: remote
 // read/write/CAS, alloc), the Directory's root publication
 // (src/Directory.cpp:72-83) and the Local/GlobalAllocator
 // (include/LocalAllocator.h, GlobalAllocator.h) are taken by: plain HBM

@@ -29,6 +29,9 @@
 #include <cstring>
 
 #include "device_common.h"
+#include "page_fields.h"
+#include "page_io.h"
+#include "sum_line.h"
 #include "kernels.h"
 #include "lds_dma.h"
 #include "leaf_chunk.h"
@@ -111,13 +114,11 @@ __device__ __forceinline__ uint32_t apply_group(const SegArgs& a, const uint32_t
   uint32_t err = 0;
   // ---- per slot q: header, entries ---------------------------------------------
   const uint32_t* hp = buf + q * kPageDwords;
-  const uint32_t h2 = hp[2], h3 = hp[3], h4 = hp[4], h7 = hp[7], h8 = hp[8], h9 = hp[9],
-                 h10 = hp[10], z = hp[kOffLeafRear / 4];
-  const uint64_t leftmost = (uint64_t)((h2 >> 8) | (h3 << 24)) |
-                            ((uint64_t)((h3 >> 8) | (h4 << 24)) << 32);
-  const uint32_t fver = h2 & 0xFF;
-  const uint64_t lowest = (uint64_t)h7 | ((uint64_t)h8 << 32);
-  const uint64_t highest = (uint64_t)h9 | ((uint64_t)h10 << 32);
+  const PageHdr hd = read_hdr(hp);
+  const uint32_t z = hp[kDwLeafRear];
+  const uint64_t leftmost = hd.leftmost;
+  const uint32_t fver = hd.fver;
+  const uint64_t lowest = hd.lowest, highest = hd.highest;
   const bool qpok = (shfl32(pok ? 1u : 0u, q) != 0) && locked;  // buf slot q holds it
   const bool cons = leftmost == 0 && fver == (z & 0xFF);
   if (ballot(qpok && !cons)) err |= kErrInconsistent;

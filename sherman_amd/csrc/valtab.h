@@ -56,7 +56,7 @@ __host__ __device__ __forceinline__ bool vt_bucket_of(uint64_t lo, uint32_t shif
 
 // The probe's per-slot predicates (w: one slot as key lo, key hi, value lo,
 // value hi), shared by the lane that loads a whole bucket (vt_probe) and the
-// eight lanes that load one slot each (get.hip's cooperative probe).
+// eight lanes that load one slot each (get_sum.hip's cooperative probe).
 // slot 0 carries the dead marker
 __device__ __forceinline__ bool vt_slot_dead(const u32x4& w) {
   return (w.x & w.y) == 0xFFFFFFFFu;

@@ -1,4 +1,4 @@
-"""Host model of which path answers a batched get (get.hip k_get_sum), in
+"""Host model of which path answers a batched get (get_sum.hip k_get_sum), in
 numpy, sharing no code with the library.
 
 A read phase's get reads its key's bucket of the key-value table first
@@ -32,7 +32,7 @@ constant:
 One exception to rule 1, stated here because the classes above do not see
 it: an ABSENT key of class "value" whose top 32 offset bits equal the split
 point of its entry's second leaf (ties()) is started at that leaf with a safe
-start kept aside, and get.hip answers "absent" from the entry only without
+start kept aside, and get_sum.hip answers "absent" from the entry only without
 one; such a key walks and may read a false candidate.  Stored keys are never
 affected (the inline copy answers them first).  split() keeps such keys out of
 the batches held to rule 1.
@@ -94,10 +94,10 @@ def classify(keys, table, directory, flags):
 
 def ties(keys, directory):
     """Whether each key's directory lookup is a tie at a split point
-    (device_common.h dir_start_e): the entry is not in fingerprint form, the
+    (dir_entry.h dir_start_e): the entry is not in fingerprint form, the
     prefix is wider than 2^32 keys, and the top 32 bits of the key's offset
     in the prefix equal the split point of the leaf after the one it would
-    start in.  get.hip keeps a safe start for such a key and then answers
+    start in.  get_sum.hip keeps a safe start for such a key and then answers
     "absent" from the leaves only."""
     keys = np.asarray(keys, dtype=U64)
     d, _ = _directory(directory)

@@ -2,7 +2,7 @@
 model that shares no code with the library (tests/dir_model.py).
 
 An exact directory is trusted for results: a usable entry that does not lead
-to a key answers "absent" (get.hip exact_miss), a value-form entry answers
+to a key answers "absent" (get_sum.hip exact_miss), a value-form entry answers
 from its inline copy (layout.h kDirVals).  The other directory tests spread
 hashed keys over 2^64 (about two per prefix), which never reaches the edges of
 the upkeep's state machine (dir_upkeep.h): 2 -> 3 keys (the value form ends),

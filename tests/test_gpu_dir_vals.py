@@ -1,7 +1,7 @@
 """The value form of the leaf directory (layout.h kDirVals): in a read phase
 a pair-form entry of a prefix that holds at most two keys carries their
 (key, value) inline, and an exact directory's get of such a prefix is
-answered by its entry alone (get.hip).  The copies must equal the tree for as
+answered by its entry alone (get_sum.hip).  The copies must equal the tree for as
 long as the flag is trusted: builds, repairs, split pages and the chunks'
 upkeep (dir_upkeep.h) are checked here against the CPU oracle and by
 shm__dir_verify, which compares every value-form entry with the tree.

@@ -1,4 +1,4 @@
-"""The two forms of k_get_sum's front (get.hip) behind a bucket table: the
+"""The two forms of k_get_sum's front (get_sum.hip) behind a bucket table: the
 cooperative probe (SHM_GET_COOP: eight lanes load one bucket line, the owner
 lane gets vt_probe's answer back) and the packing of the gets the table does
 not answer into the block's lowest waves (SHM_GET_PACK).  Every batch runs on
