@@ -34,13 +34,9 @@ Python exchange below remains the logic the gloo tests check.
 """
 import torch
 
+from ._abi import from_i64, to_i64
 
 _SIGN = -(1 << 63)  # int64 bit pattern of 2^63
-
-
-def _u64(x):
-    """Python int in [0, 2^64) -> the int64 holding the same bits."""
-    return x - (1 << 64) if x >= (1 << 63) else x
 
 
 def _split_list(splitters, world):
@@ -48,7 +44,7 @@ def _split_list(splitters, world):
     or an int64 tensor holding the bits)."""
     if torch.is_tensor(splitters):
         splitters = splitters.tolist()
-    sp = [int(x) & ((1 << 64) - 1) for x in splitters]
+    sp = [from_i64(int(x)) for x in splitters]
     if len(sp) != world - 1:
         raise ValueError("world - 1 splitters")
     if any(a > b for a, b in zip(sp, sp[1:])) or (sp and sp[-1] == (1 << 64) - 1):
@@ -62,7 +58,7 @@ def owner_of(keys, world, splitters=None):
     boundaries, repeats allowed): the number of splitters <= k, so a key equal
     to a repeated splitter goes to the highest shard that starts there."""
     if splitters is not None:
-        sp = torch.tensor([_u64(x) ^ _SIGN for x in _split_list(splitters, world)],
+        sp = torch.tensor([to_i64(x) ^ _SIGN for x in _split_list(splitters, world)],
                           dtype=torch.int64, device=keys.device)
         # the sign bit flipped: signed order of the int64 = unsigned order of the u64
         return torch.bucketize(keys ^ _SIGN, sp, right=True)
@@ -78,7 +74,7 @@ def shard_bounds(world, device, splitters=None):
         inner = _split_list(splitters, world)
     else:
         inner = [(s * (1 << 64) + world - 1) // world for s in range(1, world)]
-    b = [0] + [_u64(x) for x in inner] + [_u64((1 << 64) - 1)]
+    b = [0] + [to_i64(x) for x in inner] + [to_i64((1 << 64) - 1)]
     return torch.tensor(b, dtype=torch.int64, device=device)
 
 
@@ -141,7 +137,7 @@ def sample_splitters(keys, world, dist, group=None, per_rank=1024):
         i = int(torch.searchsorted(cw, torch.tensor(total * j / world - 1e-9, dtype=torch.float64,
                                                     device=dev)))
         i = min(i, k.numel() - 1)
-        v = (int(k[i]) ^ _SIGN) & ((1 << 64) - 1)
+        v = from_i64(int(k[i]) ^ _SIGN)
         out.append(min(v + 1, (1 << 64) - 2))
     return out
 

@@ -30,11 +30,11 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, host, lib_ok, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from rscan_model import RScanModel  # noqa: E402
 from scan_model import ScanModel  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
 ERR_KEYMAX = 1 << 31  # kernels.h kErrKeyMax
 ARENA = 64 << 20
@@ -49,21 +49,6 @@ SHIFT = 50
 
 def anchor(i):
     return (np.asarray(i, dtype=U64) + U64(1)) << U64(SHIFT)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 # ---- chunks -----------------------------------------------------------------

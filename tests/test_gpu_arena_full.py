@@ -45,28 +45,19 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import arena_model as am  # noqa: E402
 import get_paths  # noqa: E402
+import gpu_helpers  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import assert_same, dev, gpu_search, host, lib_ok, U64  # noqa: E402
 import state_model as sm  # noqa: E402
 import test_gpu_tall as tall  # noqa: E402
 import valtab_model  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
-U64 = np.uint64
 PAGE = 1024
 KEY_MAX = (1 << 64) - 1
 NOMEM, HANDOFF, KEYMAX_BIT = 0x80, 0x100, 1 << 31  # kErrNoMem, kErrHandoff, kErrKeyMax
 ROOM = 64 * PAGE  # free pages of the oracles that take a chunk whole
 SPARES = tuple(range(8))  # the sweep; the test fails if `need` is not inside it
-
-dev, host, gpu_search, assert_same = tall.dev, tall.host, tall.gpu_search, tall.assert_same
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
-
 
 def contents(orc):
     k, v = orc.dump()
@@ -390,10 +381,7 @@ def test_queued_search_after_a_failing_chunk(lib_ok):
 
 # ---- B: arenas filled by inserts -------------------------------------------------
 def gen_keys(t, first, n):
-    k = torch.empty(n, dtype=torch.int64, device="cuda")
-    t.gen_keys(first, n, k)
-    torch.cuda.synchronize()
-    k = host(k).copy()
+    k = gpu_helpers.gen_keys(t, first, n)
     return k[(k != U64(KEY_MAX)) & (k != U64(0))]
 
 

@@ -22,31 +22,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bulk_model as bm  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, gpu_search, host, lib_ok, SENT, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from rscan_model import RScanModel  # noqa: E402
 from scan_model import ScanModel  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
 PAGE = 1024
 ARENA = 64 << 20
 MAX_BATCH = 1 << 14
-SENT = 0x5A5A5A5A5A5A5A5A
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, dtype=U64).view(np.int64)).cuda()  # a writable copy
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,15 +42,6 @@ def shape(n, lf, inf, node_id=0):
     for a in (keys, vals, img):
         a.setflags(write=False)
     return keys, vals, img, root, pl
-
-
-def gpu_search(t, keys):
-    k = dev(keys)
-    v = torch.full_like(k, SENT)
-    f = torch.full((k.numel(),), 7, dtype=torch.uint8, device=k.device)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    return host(v), f.cpu().numpy()
 
 
 def assert_gets(t, keys, vals, absent, what):

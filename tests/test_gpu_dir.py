@@ -25,56 +25,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dir_model  # noqa: E402
 import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import (assert_same, dev, gen_keys, gpu_search,  # noqa: E402
+                         gpu_search_stats, lib_ok, U64)
 from oracle.pyoracle import OracleTree  # noqa: E402
 
-U64 = np.uint64
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-def gen_keys(t, first, n):
-    """key(i) = CityHash64(i) + 1 for i = first .. first + n - 1 (the
-    device generator; test_device_cityhash_matches_oracle pins it)."""
-    k = torch.empty(n, dtype=torch.int64, device="cuda")
-    t.gen_keys(first, n, k)
-    torch.cuda.synchronize()
-    return host(k).copy()
-
-
-def gpu_search(t, keys, stats=False):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device="cuda")
-    if stats:
-        t.profile(False, index_stats=True)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    st = None
-    if stats:
-        st = t.index_stats()
-        t.profile(False)
-    return host(v), f.cpu().numpy(), st
-
-
-def assert_same(probe, ov, of, gv, gf):
-    bad = np.nonzero((of != gf) | (ov != gv))[0]
-    if bad.size:
-        lines = [f"key={int(probe[i]):#x} oracle=({of[i]},{int(ov[i])}) gpu=({gf[i]},{int(gv[i])})"
-                 for i in bad[:8]]
-        raise AssertionError(f"{bad.size} mismatches:\n" + "\n".join(lines))
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def loaded(n0, maint="always", arena=512 << 20, max_batch=1 << 18):
@@ -131,8 +85,8 @@ def _splitting_chunks(form, table=True):
     probe = base[rng.integers(0, n0, 1 << 15)]
     reads = 5 if form == "pairs" else 1  # four searches without an insert: the read phase
     for _ in range(reads):
-        gv, gf, _ = gpu_search(t, probe)
-    gv, gf, st0 = gpu_search(t, probe, stats=True)
+        gv, gf = gpu_search(t, probe)
+    gv, gf, st0 = gpu_search_stats(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     d0 = t.dir_stats()
     assert d0["form"] == form and d0["maintained"], d0
@@ -162,7 +116,7 @@ def _splitting_chunks(form, table=True):
     stored, _ = orc.dump()
     probe2 = np.concatenate([stored[rng.integers(0, stored.size, 1 << 15)],
                              gen_keys(t, nid, 4096)])  # + never stored
-    gv, gf, st1 = gpu_search(t, probe2, stats=True)
+    gv, gf, st1 = gpu_search_stats(t, probe2)
     assert_same(probe2, *orc.search_batch(probe2), gv, gf)
     d1 = t.dir_stats()
     assert d1["builds"] == d0["builds"], (d0, d1)  # no rebuild: the chunks kept it
@@ -231,7 +185,7 @@ def test_without_upkeep_the_same_chunks_stay_exact(lib_ok):
     t.insert_batch(dev(new), dev(nv))
     orc.apply_batch(new, nv)
     probe2 = np.concatenate([probe, new[:8192]])
-    gv, gf, st = gpu_search(t, probe2, stats=True)  # the first search after: stale pairs
+    gv, gf, st = gpu_search_stats(t, probe2)  # the first search after: stale pairs
     assert_same(probe2, *orc.search_batch(probe2), gv, gf)
     assert st["dir_fp_hits"] < st["hits"], st  # new keys and moved slots missed the pairs
     orc.close()
@@ -254,7 +208,7 @@ def test_directory_allocation_failure_keeps_the_tree_working(lib_ok):
     rng = np.random.default_rng(9)
     probe = np.concatenate([base[rng.integers(0, n0, 1 << 14)], gen_keys(t, n0 + 1, 1024)])
     want = orc.search_batch(probe)
-    gv, gf, _ = gpu_search(t, probe)  # the write phase's fingerprint directory, sized
+    gv, gf = gpu_search(t, probe)  # the write phase's fingerprint directory, sized
     assert_same(probe, *want, gv, gf)
     d = t.dir_stats()
     assert d["form"] == "fingerprints", d
@@ -263,7 +217,7 @@ def test_directory_allocation_failure_keeps_the_tree_working(lib_ok):
     t.dir_config(mem_limit=d["bytes"])
     builds = []
     for _ in range(10):  # into the read phase and on
-        gv, gf, _ = gpu_search(t, probe)
+        gv, gf = gpu_search(t, probe)
         assert_same(probe, *want, gv, gf)
         builds.append(t.dir_stats()["builds"])
     d1 = t.dir_stats()
@@ -276,7 +230,7 @@ def test_directory_allocation_failure_keeps_the_tree_working(lib_ok):
     t2.dir_config(mem_limit=4096)
     t2.insert_batch(dev(base), dev(bv))
     for _ in range(5):
-        gv, gf, _ = gpu_search(t2, probe)
+        gv, gf = gpu_search(t2, probe)
         assert_same(probe, *want, gv, gf)
     assert t2.dir_stats()["form"] == "none"
     t2.close()
@@ -309,7 +263,7 @@ def test_insert_every_cycles_build_once(lib_ok):
         assert_dir_exact(t)
         for j in range(8):
             q = np.concatenate([qs[j % 4], new[j::8]])
-            gv, gf, _ = gpu_search(t, q)
+            gv, gf = gpu_search(t, q)
             if j in (0, 7):
                 assert_same(q, *orc.search_batch(q), gv, gf)
     d = t.dir_stats()
@@ -346,14 +300,14 @@ def test_upkeep_policy_idle_and_write_only_streams(lib_ok):
     assert_dir_exact(t)
     # update-only chunks, searched between: idle upkeeps stop the upkeep
     for r in range(5):
-        gv, gf, _ = gpu_search(t, probe)
+        gv, gf = gpu_search(t, probe)
         assert_same(probe, *orc.search_batch(probe), gv, gf)
         upd = base[rng.integers(0, n0, 4000)]
         t.insert_batch(dev(upd), dev(upd ^ U64(100 + r)))
         orc.apply_batch(upd, upd ^ U64(100 + r))
         t.synchronize()
     assert t.dir_stats()["exact"] == 0
-    gv, gf, _ = gpu_search(t, probe)
+    gv, gf = gpu_search(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     # a fresh build makes it exact again; a chunk with no search before it
     # (the second one) stops the upkeep at once
@@ -373,10 +327,10 @@ def test_upkeep_policy_idle_and_write_only_streams(lib_ok):
         t.synchronize()
     assert t.dir_stats()["exact"] == 0
     ok_, ov = orc.dump()
-    gv, gf, _ = gpu_search(t, ok_)
+    gv, gf = gpu_search(t, ok_)
     assert bool(gf.all()) and np.array_equal(gv, ov)
     miss = gen_keys(t, 10**9 + 7, 2000)
-    gv, gf, _ = gpu_search(t, miss)
+    gv, gf = gpu_search(t, miss)
     assert_same(miss, *orc.search_batch(miss), gv, gf)
     orc.close()
     t.close()
@@ -416,14 +370,14 @@ def test_exact_directory_places_new_keys_through_many_chunks(lib_ok, reads):
         probe = np.concatenate([k, stored[rng.integers(0, stored.size, 4000)],
                                 gen_keys(t, nid + 10**7, 500)])
         for _ in range(reads):
-            gv, gf, _ = gpu_search(t, probe)
+            gv, gf = gpu_search(t, probe)
         assert_same(probe, *orc.search_batch(probe), gv, gf)
     d = t.dir_stats()
     assert d["maintained"] and d["form"] == ("pairs" if reads == 5 else "fingerprints"), d
     rc, oc = orc.check()
     assert rc == 0 and t.check()["keys"] == oc["keys"]
     ok_, ov = orc.dump()
-    gv, gf, _ = gpu_search(t, ok_)
+    gv, gf = gpu_search(t, ok_)
     assert bool(gf.all()) and np.array_equal(gv, ov)
     orc.close()
     t.close()
@@ -446,7 +400,7 @@ def test_page_check_flag_on_the_fast_path(lib_ok):
     for r in range(3):
         probe = np.concatenate([base[rng.integers(0, n0, 1 << 14)], gen_keys(t, 10**9 + r, 2000)])
         for _ in range(5 if r == 1 else 1):
-            gv, gf, _ = gpu_search(t, probe)
+            gv, gf = gpu_search(t, probe)
             assert_same(probe, *orc.search_batch(probe), gv, gf)
         new = gen_keys(t, n0 + 1 + r * 20000, 20000)
         nv = new ^ U64(5)
@@ -501,7 +455,7 @@ def test_random_phases_against_the_oracle(lib_ok, seed):
         probe = np.concatenate([k[:2000], stored[rng.integers(0, stored.size, 3000)],
                                 gen_keys(t, 10**9 + 1000 * r, 300)])
         for _ in range(int(rng.integers(0, 7))):
-            gv, gf, _ = gpu_search(t, probe)
+            gv, gf = gpu_search(t, probe)
             assert_same(probe, *orc.search_batch(probe), gv, gf)
         if r % 7 == 3:
             lo = stored[rng.integers(0, stored.size, 64)]
@@ -515,7 +469,7 @@ def test_random_phases_against_the_oracle(lib_ok, seed):
     rc, oc = orc.check()
     assert rc == 0 and t.check()["keys"] == oc["keys"]
     ok_, ov = orc.dump()
-    gv, gf, _ = gpu_search(t, ok_)
+    gv, gf = gpu_search(t, ok_)
     assert bool(gf.all()) and np.array_equal(gv, ov)
     orc.close()
     t.close()

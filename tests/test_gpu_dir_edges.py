@@ -54,9 +54,9 @@ import dir_model as dm  # noqa: E402
 import get_paths as gp  # noqa: E402
 import valtab_model as vm  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import assert_same, dev, gen_keys, gpu_search, lib_ok, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
-U64 = np.uint64
 N0 = 1 << 14
 ARENA = 64 << 20
 MB = 1 << 14
@@ -64,53 +64,8 @@ MIN_TARGETS = 32
 LEAF_SLOTS = 54
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-def gen_keys(t, first, n, keyspace=0):
-    k = torch.empty(n, dtype=torch.int64, device="cuda")
-    t.gen_keys(first, n, k, keyspace=keyspace)
-    torch.cuda.synchronize()
-    return host(k).copy()
-
-
-def gpu_search(t, keys, stats=False):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device="cuda")
-    if stats:
-        t.profile(False, index_stats=True)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    st = None
-    if stats:
-        st = t.index_stats()
-        t.profile(False)
-    return host(v), f.cpu().numpy(), st
-
-
-def assert_same(probe, ov, of, gv, gf):
-    bad = np.nonzero((of != gf) | (ov != gv))[0]
-    if bad.size:
-        lines = [f"key={int(probe[i]):#x} oracle=({of[i]},{int(ov[i])}) gpu=({gf[i]},{int(gv[i])})"
-                 for i in bad[:8]]
-        raise AssertionError(f"{bad.size} mismatches:\n" + "\n".join(lines))
-
-
 def u64s(xs):
     return np.array([int(x) & ((1 << 64) - 1) for x in xs], dtype=U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 class Rig:
@@ -218,7 +173,7 @@ class Rig:
         ("pair", "value", "fp") the model must have found to check"""
         t = self.t
         probe = self.probes(touched)
-        gv, gf, _ = gpu_search(t, probe)  # (a)
+        gv, gf = gpu_search(t, probe)  # (a)
         assert_same(probe, *self.orc.search_batch(probe), gv, gf)
         self.refresh()  # (b)
         okeys, ovals = self.orc.dump()
@@ -648,7 +603,7 @@ def test_twelve_keys_of_one_fingerprint(lib_ok):
     ok = tg.unsplit()
     assert np.all(tg.counts()[ok] == 12)
     n = expect_state(rig, tg, flagged=True, label="fp12")
-    gv, gf, _ = gpu_search(rig.t, own.ravel())
+    gv, gf = gpu_search(rig.t, own.ravel())
     assert bool(gf.all())
     print(f"scenario 5: unsplit targets {n}, model checked {rig.checked}, {time.time() - t0:.2f} s")
     assert n >= MIN_TARGETS, n
@@ -678,7 +633,7 @@ def test_both_ends_of_the_key_space(lib_ok, form):
         rig.apply(k, rig.values(k.size))
         rig.check(concat([k, ends]), expect=("pair",) if form == "pairs" else ())
     assert rig.t.stats()["pages_used"] >= pages0 + 8, (pages0, rig.t.stats())
-    gv, gf, _ = gpu_search(rig.t, concat([asc, desc]))
+    gv, gf = gpu_search(rig.t, concat([asc, desc]))
     assert bool(gf.all())
     print(f"scenario 6 [{form}]: model checked {rig.checked}, {time.time() - t0:.2f} s")
     rig.finish()

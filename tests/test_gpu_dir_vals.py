@@ -25,58 +25,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dir_model  # noqa: E402
 import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import (assert_same, dev, gen_keys, gpu_search,  # noqa: E402
+                         gpu_search_stats, host, lib_ok, U64)
 from oracle.pyoracle import OracleTree  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U64 = np.uint64
 N0 = 1 << 18
 ARENA = 512 << 20
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-def gen_keys(t, first, n):
-    k = torch.empty(n, dtype=torch.int64, device="cuda")
-    t.gen_keys(first, n, k)
-    torch.cuda.synchronize()
-    return host(k).copy()
-
-
-def gpu_search(t, keys, stats=False):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device="cuda")
-    if stats:
-        t.profile(False, index_stats=True)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    st = None
-    if stats:
-        st = t.index_stats()
-        t.profile(False)
-    return host(v), f.cpu().numpy(), st
-
-
-def assert_same(probe, ov, of, gv, gf):
-    bad = np.nonzero((of != gf) | (ov != gv))[0]
-    if bad.size:
-        lines = [f"key={int(probe[i]):#x} oracle=({of[i]},{int(ov[i])}) gpu=({gf[i]},{int(gv[i])})"
-                 for i in bad[:8]]
-        raise AssertionError(f"{bad.size} mismatches:\n" + "\n".join(lines))
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def loaded(maint="always", max_batch=1 << 18, **kw):
@@ -184,7 +140,7 @@ def _small_prefixes(table):
     else:  # the value form's share is q: a prefix of at most two keys is held inline
         assert np.array_equal(cls == gp.VALUE, px.held(probe) <= 2), gp.tally(cls)
     absent = gen_keys(t, N0 + 1, 1 << 13)
-    gv, gf, _ = gpu_search(t, absent)
+    gv, gf = gpu_search(t, absent)
     assert_same(absent, *orc.search_batch(absent), gv, gf)
     v = verify_clean(t)
     assert v["vals_checked"] > 0, v
@@ -328,7 +284,7 @@ def test_chunks_without_upkeep_end_the_trust_without_the_table(lib_ok, how):
 def _stored_batch_reads_every_hit(t, orc, base):
     rng = np.random.default_rng(24)
     probe = np.concatenate([base[rng.integers(0, N0, 1 << 15)], gen_keys(t, N0 + 1, 1 << 12)])
-    gv, gf, st = gpu_search(t, probe, stats=True)
+    gv, gf, st = gpu_search_stats(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     assert st["hits"] == 1 << 15 and st["entry_reads"] >= st["hits"], st
 
@@ -407,7 +363,7 @@ def test_ordering_on_a_second_stream_does_not_reach_the_upkeep(lib_ok):
         assert_same(probe_h, ov, of, host(gv), gf.cpu().numpy())
         orc.apply_batch(batches[i][2], batches[i][3])
     orc.apply_batch(batches[8][2], batches[8][3])
-    gv, gf, _ = gpu_search(t, probe_h)
+    gv, gf = gpu_search(t, probe_h)
     assert_same(probe_h, *orc.search_batch(probe_h), gv, gf)
     v1 = verify_clean(t)
     assert v1["vals_checked"] > 0, v1

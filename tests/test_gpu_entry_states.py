@@ -27,29 +27,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dir_model  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, gpu_search, host, lib_ok, SENT, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from scan_model import ScanModel  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
 ARENA = 64 << 20
 MAX_BATCH = 1 << 14
-SENT = 0x5A5A5A5A5A5A5A5A
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 @pytest.fixture(scope="module")
@@ -73,15 +57,6 @@ def load(states, **tree_args):
     t = shm.Tree(arena_bytes=ARENA, max_batch=MAX_BATCH, **tree_args)
     t.load_image(img, root)
     return t, orc, info
-
-
-def gpu_search(t, keys):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device=k.device)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    return host(v), f.cpu().numpy()
 
 
 def probes(info):

@@ -23,31 +23,15 @@ import bulk_model as bm  # noqa: E402
 import export_model as em  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, gpu_search, host, lib_ok, SENT, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from rscan_model import RScanModel  # noqa: E402
 from scan_model import ScanModel  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
 PAGE = 1024
 ARENA = 64 << 20
 MAX_BATCH = 1 << 14
-SENT = 0x5A5A5A5A5A5A5A5A
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, dtype=U64).view(np.int64)).cuda()  # a writable copy
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def tree(**kw):
@@ -79,15 +63,6 @@ def assert_export(t, keys, vals, lo=0, hi=KEY_MAX, what=""):
     bad = np.nonzero((gk[:n] != keys) | (gv[:n] != vals))[0]
     assert bad.size == 0, (what, bad.size, int(bad[0]), hex(int(gk[bad[0]])), hex(int(keys[bad[0]])))
     assert t.last_error()["bits"] == 0, (what, t.last_error())
-
-
-def gpu_search(t, keys):
-    k = dev(keys)
-    v = torch.full_like(k, SENT)
-    f = torch.full((k.numel(),), 7, dtype=torch.uint8, device=k.device)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    return host(v), f.cpu().numpy()
 
 
 def assert_gets(t, keys, vals, absent, what):

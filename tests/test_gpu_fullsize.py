@@ -17,20 +17,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import host, lib_ok, U64  # noqa: E402
 from oracle.pyoracle import OracleTree, op_mix, zipf_fill  # noqa: E402
 
-U64 = np.uint64
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def build_stream(t, n, chunk=1 << 20):

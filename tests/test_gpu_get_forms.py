@@ -30,22 +30,18 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import get_paths as gp  # noqa: E402
 import valtab_model as vm  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from sherman_amd.shard import shard_range  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U64 = np.uint64
 KEY_MAX = U64(shm.KEY_MAX)
 N0 = 1 << 16
 MB = 1 << 16
 ARENA = 128 << 20
 TPB = 256  # kernels.h kGetSumTPB
 COMBOS = [(0, 0), (0, 1), (1, 0), (1, 1)]  # (SHM_GET_COOP, SHM_GET_PACK)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
 
 
 def hashed_keys(first, n):

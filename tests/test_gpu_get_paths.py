@@ -29,20 +29,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dir_model as dm  # noqa: E402
 import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import lib_ok, U64  # noqa: E402
 import test_gpu_dir_edges as ed  # noqa: E402
 import test_gpu_dir_vals as dv  # noqa: E402
 import valtab_model as vm  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
-U64 = np.uint64
 T, V, L = gp.TABLE, gp.VALUE, gp.LEAF
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def directory_of(t):

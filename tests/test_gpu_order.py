@@ -24,17 +24,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import order_cases as oc  # noqa: E402
 import order_model as om  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, host, U64  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, dtype=U64).view(np.int64)).cuda()  # a writable copy
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
 
 
 @pytest.fixture(scope="module")

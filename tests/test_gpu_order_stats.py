@@ -24,31 +24,15 @@ import bulk_model as bm  # noqa: E402
 import export_model as em  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, host, lib_ok, SENT, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
 PAGE = 1024
 ARENA = 64 << 20
 MAX_BATCH = 1 << 14
-SENT = 0x5A5A5A5A5A5A5A5A
 EDGE = 40      # the first and last keys / ranks that a strided query set keeps
 DENSE = 300    # up to here every key / rank is queried
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, dtype=U64).view(np.int64)).cuda()  # a writable copy
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def tree(**kw):

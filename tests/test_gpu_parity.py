@@ -23,26 +23,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import get_paths as gp  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import assert_same, dev, gpu_search, host, lib_ok, U64  # noqa: E402
 from oracle.pyoracle import OracleTree, op_mix, to_key, zipf_fill  # noqa: E402
 
-U64 = np.uint64
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-def gpu_search(tree, keys):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device=k.device)
-    tree.search_batch(k, v, f)
-    tree.synchronize()
-    return host(v), f.cpu().numpy()
 
 
 def gpu_insert(tree, keys, vals):
@@ -54,21 +37,6 @@ def hashed_keys(lo, hi):
     # CityHash64 restatement on device vs oracle is checked separately; here
     # use the oracle's generator so both sides see identical streams
     return np.array([to_key(int(x)) for x in i], dtype=U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
-
-
-def assert_same(probe, ov, of, gv, gf):
-    bad = np.nonzero((of != gf) | (ov != gv))[0]
-    if bad.size:
-        lines = [f"key={int(probe[i]):#x} oracle=({of[i]},{int(ov[i])}) gpu=({gf[i]},{int(gv[i])})"
-                 for i in bad[:8]]
-        raise AssertionError(f"{bad.size} mismatches:\n" + "\n".join(lines))
 
 
 def compare_contents(tree, orc):

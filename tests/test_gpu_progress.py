@@ -27,9 +27,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, host, lib_ok, U64  # noqa: E402
 from oracle.pyoracle import OracleTree, to_key  # noqa: E402
 
-U64 = np.uint64
 
 HOG_SRC = r"""
 import ctypes, sys, time
@@ -44,14 +44,6 @@ print("started", flush=True)
 assert hip.hipDeviceSynchronize() == 0
 print("done", flush=True)
 """
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
 
 
 def keys_of(t, lo, hi):
@@ -72,13 +64,6 @@ def compare_contents(t, orc):
     assert bool(f.all()), f"{int((f == 0).sum())} oracle keys missing on GPU"
     assert np.array_equal(host(v), ov)
     assert t.check()["keys"] == ok.size
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def start_hog(ticks, blocks=240):

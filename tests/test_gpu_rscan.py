@@ -24,23 +24,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import arena_model as am  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, host, lib_ok, SENT, U64  # noqa: E402
 import test_gpu_arena_full as full  # noqa: E402
 import test_gpu_tall as tall  # noqa: E402
 from oracle.pyoracle import OracleTree, to_key  # noqa: E402
 from rscan_model import KEY_MAX, RScanModel  # noqa: E402
 
-U64 = np.uint64
-SENT = 0x5A5A5A5A5A5A5A5A
 ARENA = 64 << 20
 TOP = 1 << 63
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
 
 
 def hashed_keys(lo, hi):
@@ -49,13 +40,6 @@ def hashed_keys(lo, hi):
 
 def u64(*xs):
     return np.array([int(x) for x in xs], dtype=U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def put(t, orc, keys, vals):

@@ -22,32 +22,16 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, host, lib_ok, SENT, U64  # noqa: E402
 from oracle.pyoracle import OracleTree, to_key  # noqa: E402
 from scan_model import KEY_MAX, ScanModel  # noqa: E402
 
-U64 = np.uint64
-SENT = 0x5A5A5A5A5A5A5A5A
 ARENA = 64 << 20
 TOP = 1 << 63
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
 def hashed_keys(lo, hi):
     return np.array([to_key(i) for i in range(lo, hi)], dtype=U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def put(t, orc, keys, vals):

@@ -31,22 +31,15 @@ import bulk_model  # noqa: E402
 import dir_model  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import dev, gpu_search, host, lib_ok, U64  # noqa: E402
 import state_model as sm  # noqa: E402
 import test_gpu_tall as tall  # noqa: E402
 
-U64 = np.uint64
 ARENA = 64 << 20
 MAX_BATCH = 1 << 12
 HANDOFF = 0x100  # kErrHandoff
 
-dev, host, gpu_search, assert_side = tall.dev, tall.host, tall.gpu_search, tall.assert_side
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
+assert_side = tall.assert_side
 
 
 def tree(**args):

@@ -36,35 +36,19 @@ import dir_model  # noqa: E402
 from arena_model import hot_chunk  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import assert_same, dev, gpu_search, host, lib_ok, SENT, U64  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 from scan_model import ScanModel  # noqa: E402
 import state_model  # noqa: E402
 
-U64 = np.uint64
 KEY_MAX = (1 << 64) - 1
 ARENA = 64 << 20
 MAX_BATCH = 1 << 14
 SPARE = 16 << 20
-SENT = 0x5A5A5A5A5A5A5A5A
 HANDOFF = 0x100  # kErrHandoff
 
 # shm__upper_force flags of the four writer modes
 MODES = {"default": 0, "upper": 4, "lists": 6, "abort": 7}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=U64).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,23 +80,6 @@ def load(root_level, path, root_full, page_ver=1, wrapped=True, **tree_args):
                          "keys": info["n_keys"]}
     assert t.stats()["height"] == root_level + 1 and t.stats()["root_level"] == root_level
     return t, orc, info
-
-
-def gpu_search(t, keys):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device=k.device)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    return host(v), f.cpu().numpy()
-
-
-def assert_same(probe, ov, of, gv, gf, what):
-    bad = np.nonzero((of != gf) | (ov != gv))[0]
-    if bad.size:
-        lines = [f"key={int(probe[i]):#x} oracle=({of[i]},{int(ov[i])}) gpu=({gf[i]},{int(gv[i])})"
-                 for i in bad[:8]]
-        raise AssertionError(f"{what}: {bad.size} gets differ:\n" + "\n".join(lines))
 
 
 def probes(info, stored):

@@ -54,26 +54,17 @@ import dir_model  # noqa: E402
 import get_paths  # noqa: E402
 import image_builder as ib  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import assert_same, dev, gpu_search, host, lib_ok, U64  # noqa: E402
 import test_gpu_arena_full as full  # noqa: E402
 import test_gpu_bulk as bulk  # noqa: E402
 import test_gpu_tall as tall  # noqa: E402
 import valtab_model  # noqa: E402
 from oracle.pyoracle import OracleTree  # noqa: E402
 
-U64 = np.uint64
 PAGE = ib.PAGE
 KEY_MAX = (1 << 64) - 1
 KINDS = (ib.ABSENT, ib.SHADOW, ib.DELETED)
 SWEPT = KINDS + (ib.OUTSIDE,)  # the kinds a sweep would take: valid entries
-
-dev, host, gpu_search, assert_same = tall.dev, tall.host, tall.gpu_search, tall.assert_same
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 # ---- the readers ------------------------------------------------------------------

@@ -23,58 +23,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import valtab_model as vm  # noqa: E402
 from get_paths import with_env, without_table  # noqa: E402
 import sherman_amd as shm  # noqa: E402
+from gpu_helpers import (assert_same, dev, gen_keys, gpu_search,  # noqa: E402
+                         gpu_search_stats, host, lib_ok, U64)
 from oracle.pyoracle import OracleTree  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U64 = np.uint64
 N0 = 1 << 18
 ARENA = 512 << 20
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(U64)
-
-
-def gen_keys(t, first, n):
-    k = torch.empty(n, dtype=torch.int64, device="cuda")
-    t.gen_keys(first, n, k)
-    torch.cuda.synchronize()
-    return host(k).copy()
-
-
-def gpu_search(t, keys, stats=False):
-    k = dev(keys)
-    v = torch.empty_like(k)
-    f = torch.empty(k.numel(), dtype=torch.uint8, device="cuda")
-    if stats:
-        t.profile(False, index_stats=True)
-    t.search_batch(k, v, f)
-    t.synchronize()
-    st = None
-    if stats:
-        st = t.index_stats()
-        t.profile(False)
-    return host(v), f.cpu().numpy(), st
-
-
-def assert_same(probe, ov, of, gv, gf):
-    bad = np.nonzero((of != gf) | (ov != gv))[0]
-    if bad.size:
-        lines = [f"key={int(probe[i]):#x} oracle=({of[i]},{int(ov[i])}) gpu=({gf[i]},{int(gv[i])})"
-                 for i in bad[:8]]
-        raise AssertionError(f"{bad.size} mismatches:\n" + "\n".join(lines))
-
-
-@pytest.fixture(scope="module")
-def lib_ok():
-    assert torch.cuda.is_available(), "GPU test without a GPU"
-    shm.lib()
-    return True
 
 
 def loaded(maint="always", max_batch=1 << 18, keys=None, mem_limit=0, **kw):
@@ -149,14 +105,14 @@ def test_build_answers_most_gets_from_one_bucket(lib_ok):
     probe = base[rng.integers(0, N0, 1 << 15)]
     p = float(np.mean(bk.count[bk.of(probe)] <= vm.SLOTS))
     assert p > 0.9, p  # uniform keys, four per bucket: 0.948
-    gv, gf, s = gpu_search(t, probe, stats=True)
+    gv, gf, s = gpu_search_stats(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     print(f"p={p:.4f} gets={s['gets']} entry_reads={s['entry_reads']} "
           f"dir_fp_hits={s['dir_fp_hits']} bound={1.05 * (1 - p) * s['gets']:.0f}")
     assert s["dir_fp_hits"] == s["gets"], s
     assert s["entry_reads"] <= 1.05 * (1 - p) * s["gets"], (p, s)
     absent = gen_keys(t, N0 + 1, 1 << 13)
-    gv, gf, s = gpu_search(t, absent, stats=True)
+    gv, gf, s = gpu_search_stats(t, absent)
     assert_same(absent, *orc.search_batch(absent), gv, gf)
     assert not gf.any() and s["dir_fp_hits"] <= s["hits"], s
     assert t.last_error()["bits"] == 0
@@ -232,7 +188,7 @@ def test_chunks_keep_the_table_equal_to_the_tree(lib_ok):
                                             k + U64(1), sample]))
         touched = touched[touched != U64(shm.KEY_MAX)]
         touched = np.unique(np.append(touched, U64(0)))
-        gv, gf, s = gpu_search(t, touched, stats=True)
+        gv, gf, s = gpu_search_stats(t, touched)
         assert_same(touched, *orc.search_batch(touched), gv, gf)
         model_clean(t, orc)
         vs = t.vt_stats()
@@ -287,7 +243,7 @@ def test_chunks_without_upkeep_end_the_trust(lib_ok, how):
     assert not t.dir_stats()["exact"]
     assert not t.vt_stats()["trusted"]
     probe = np.concatenate([k, base[pick[8000:12000]]])
-    gv, gf, _ = gpu_search(t, probe)
+    gv, gf = gpu_search(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     assert not t.vt_stats()["trusted"]
     orc.close()
@@ -316,7 +272,7 @@ def test_switches_read_every_hit_from_its_leaf(lib_ok, switch):
     rng = np.random.default_rng(34)
     probe = np.concatenate([big[rng.integers(0, big.size, 1 << 15)],
                             gen_keys(t, N0 + 1, 1 << 12)])
-    gv, gf, st = gpu_search(t, probe, stats=True)
+    gv, gf, st = gpu_search_stats(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     assert st["hits"] == 1 << 15 and st["entry_reads"] >= st["hits"], st
     assert t.last_error()["bits"] == 0
@@ -367,7 +323,7 @@ def test_ordering_on_a_second_stream_does_not_reach_the_table_upkeep(lib_ok):
         assert_same(probe_h, ov, of, host(gv), gf.cpu().numpy())
         orc.apply_batch(batches[i][2], batches[i][3])
     orc.apply_batch(batches[8][2], batches[8][3])
-    gv, gf, _ = gpu_search(t, probe_h)
+    gv, gf = gpu_search(t, probe_h)
     assert_same(probe_h, *orc.search_batch(probe_h), gv, gf)
     assert t.vt_stats()["trusted"]
     model_clean(t, orc)
@@ -390,7 +346,7 @@ def test_dense_keys_drop_the_table(lib_ok):
     rng = np.random.default_rng(36)
     probe = np.concatenate([dense[rng.integers(0, n, 1 << 14)],
                             np.arange(n + 1, n + 1025, dtype=U64)])
-    gv, gf, _ = gpu_search(t, probe)
+    gv, gf = gpu_search(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     assert t.vt_stats()["buckets"] == 0
     orc.close()
@@ -402,7 +358,7 @@ def test_dense_keys_drop_the_table(lib_ok):
     vs = t.vt_stats()
     assert vs["trusted"] and vs["buckets"] > 0, vs
     probe = np.concatenate([hashed[rng.integers(0, n, 1 << 14)], dense[:1024]])
-    gv, gf, _ = gpu_search(t, probe)
+    gv, gf = gpu_search(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     model_clean(t, orc)
     orc.close()
@@ -425,7 +381,7 @@ def test_memory_limit_leaves_no_table(lib_ok):
     assert vs["buckets"] == 0 and not vs["trusted"], vs
     rng = np.random.default_rng(37)
     probe = base[rng.integers(0, N0, 1 << 14)]
-    gv, gf, _ = gpu_search(t, probe)
+    gv, gf = gpu_search(t, probe)
     assert_same(probe, *orc.search_batch(probe), gv, gf)
     orc.close()
     t.close()
